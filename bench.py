@@ -73,7 +73,51 @@ def parse():
                          "tests/test_gpu_dp2.py states its tolerance).  Default fp32: the single-GPU numerics")
     ap.add_argument("--no-overlap", action="store_true",
                     help="weight-gradient GEMMs on the main stream (serial kernels: the run to put under rocprofv3 --kernel-trace)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+DUMP_SAMPLE = 1 << 21          # positions in the parameter / gradient sample of --dump-outputs (8 MB per fp32 array)
+DUMP_SEED = 20241              # fixed: the same positions in every run and every build
+
+
+def dump_outputs(d, model, loss):
+    """--dump-outputs DIR: what the last timed step handed back to its caller, so that two builds can be compared output for output
+    (same arguments -> same inputs, weights and noise):
+      loss.npy                the step's loss (float32, shape [1])
+      term_<name>.npy         the loss terms of that forward pass (model.last_terms(), float32, shape [1])
+      params_sample.npy       the parameters after the step's Adam update, at DUMP_SAMPLE fixed, seeded positions of all parameters
+                              concatenated in named_parameters() order (float32)
+      grads_sample.npy        the step's gradients (p.grad) at the same positions (float32; 0 where p.grad is None)
+      sample_index.npy        those positions (float64, exact)
+    About 32 MB in all."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+
+    def save(name, t):
+        np.save(os.path.join(d, name + ".npy"), t.detach().to("cpu", torch.float32).numpy().reshape(-1))
+    save("loss", loss)
+    for k, v in model.last_terms().items():
+        save("term_" + k, v)
+    named = list(model.named_parameters())
+    total = sum(p.numel() for _, p in named)
+    idx = torch.randint(0, total, (min(DUMP_SAMPLE, total),), generator=torch.Generator().manual_seed(DUMP_SEED)).sort().values
+    params, grads, off = [], [], 0
+    for _, p in named:
+        lo, hi = int(torch.searchsorted(idx, off)), int(torch.searchsorted(idx, off + p.numel()))
+        if hi > lo:
+            sel = (idx[lo:hi] - off).to(p.device)
+            params.append(p.detach().reshape(-1)[sel])
+            grads.append(p.grad.detach().reshape(-1)[sel] if p.grad is not None else torch.zeros(hi - lo, device=p.device))
+        off += p.numel()
+    save("params_sample", torch.cat(params))
+    save("grads_sample", torch.cat(grads))
+    np.save(os.path.join(d, "sample_index.npy"), idx.numpy().astype(np.float64))
+    log("--dump-outputs: loss, %d terms and a %d-position parameter / gradient sample written to %s" % (len(model.last_terms()), len(idx), d))
 
 
 def _cpu_model():
@@ -520,6 +564,8 @@ def main():
         dt = float(t.item())
     final_loss = float(loss.detach())
     log("timed region done: %.3f ms/step" % (1e3 * dt / a.steps))
+    if a.dump_outputs and rank == 0:        # before the legs below run more steps on the same model
+        dump_outputs(a.dump_outputs, model, loss)
     # ---- the same step on resident inputs (batches already in HBM, no read-back): what the H2D + read-back cost on this box ----
     for i in range(3):
         step(i)

@@ -2,8 +2,9 @@
 """Golden vectors for the host data path: runs the reference's OWN `read_ECPE_data` (AST-extracted from
 drl_classifier_ec_mmd_final_mul.py:631-731 at generation time, with a one-line `DataFrame.append` shim for
 pandas >= 2) on the small ECPE-format samples committed under tests/golden/ecpe/ (written for this repo, not
-copied from the reference's data) and, for an optional cross-check, on the reference's real files (row counts
-and a digest only -- no reference data is copied).   python tests/golden/gen_golden_data.py"""
+copied from the reference's data) and, for a cross-check, on two of the reference's real data files (row counts and
+a digest; the two files themselves are stored gzipped as tests/golden/ecpe/<basename>.gz so that the test needs no
+reference checkout).   python tests/golden/gen_golden_data.py"""
 import ast, hashlib, json, os, random, re, sys, types
 import pandas as pd
 

@@ -1,5 +1,6 @@
 """Host data path (read_ECPE_data / ECPEDataset / BoW vocabulary) against golden vectors produced by the
 reference's own read_ECPE_data (tests/golden/gen_golden_data.py)."""
+import gzip
 import hashlib
 import json
 import os
@@ -33,12 +34,15 @@ def test_read_ecpe_samples_match_reference(name):
     assert list(df.columns) == ["pair", "label", "emotion"]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference checkout not present (GPU box)")
 @pytest.mark.parametrize("rel", list(GOLD["reference_files"]))
-def test_read_ecpe_reference_files(rel):
+def test_read_ecpe_reference_files(rel, tmp_path):
+    """The reference's two real data files, stored gzipped as tests/golden/ecpe/<basename>.gz."""
     g = GOLD["reference_files"][rel]
+    path = tmp_path / os.path.basename(rel)
+    with gzip.open(os.path.join(HERE, "golden", "ecpe", os.path.basename(rel) + ".gz"), "rb") as f:
+        path.write_bytes(f.read())
     random.seed(42)
-    df, sizes, unpred = D.read_ECPE_data(os.path.join("/root/reference", rel), test=g["test"], language=g["language"])
+    df, sizes, unpred = D.read_ECPE_data(str(path), test=g["test"], language=g["language"])
     assert (len(df), len(sizes), unpred) == (g["rows"], g["docs"], g["num_unpred"])
     assert digest(df) == g["digest"]
 
