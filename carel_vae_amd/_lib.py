@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CAREL_HIP_LIB") or os.path.join(_HERE, "libcarel_hip.so")     # CAREL_HIP_LIB: an experiment build (tools/ablate_*.sh, tools/ab_lib.sh)
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 
 class CarelError(RuntimeError):
@@ -93,7 +93,16 @@ class TailArgs(C.Structure):
                 ("d_pair_w", C.c_void_p), ("d_pair_b", C.c_void_p), ("d_dec_w", C.c_void_p), ("d_dec_b", C.c_void_p),
                 ("d_head_w", C.c_void_p * 4), ("d_head_b", C.c_void_p * 4),
                 ("d_pooler_w", C.c_void_p), ("d_pooler_b", C.c_void_p), ("dx_last_f32", C.c_void_p),
-                ("cls_rows", C.c_void_p), ("n_rows", C.c_int32), ("serial", C.c_int32)]
+                ("cls_rows", C.c_void_p), ("n_rows", C.c_int32), ("serial", C.c_int32),
+                ("head_in_f32", C.c_void_p), ("d_head_in_f32", C.c_void_p)]
+
+
+class AdapterArgs(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("batch_padded", C.c_int32), ("seq_len", C.c_int32), ("mode", C.c_int32), ("heads", C.c_int32),
+                ("query", C.c_void_p * 2), ("q_w", C.c_void_p * 2), ("q_b", C.c_void_p * 2), ("k_w", C.c_void_p * 2),
+                ("v_w", C.c_void_p * 2), ("v_b", C.c_void_p * 2), ("o_w", C.c_void_p * 2), ("o_b", C.c_void_p * 2),
+                ("u", C.c_void_p), ("x_f32", C.c_void_p), ("out_f32", C.c_void_p), ("d_out_f32", C.c_void_p), ("dx_f32", C.c_void_p),
+                ("work", C.c_void_p)]
 
 
 class AdamArgs(C.Structure):
@@ -251,6 +260,10 @@ SIGNATURES = {
     "carel_scale_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "carel_tail_pair_dead_offset": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "carel_pair_probs": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "carel_adapter_workspace_floats": (C.c_int64, [C.c_int32] * 3),
+    "carel_adapter_build_u": (C.c_int, [C.POINTER(AdapterArgs), C.c_void_p]),
+    "carel_adapter_forward": (C.c_int, [C.POINTER(AdapterArgs), C.c_void_p]),
+    "carel_adapter_backward": (C.c_int, [C.POINTER(AdapterArgs), C.c_void_p]),
     "carel_adam_step": (C.c_int, [C.POINTER(AdamArgs), C.c_void_p]),
     "carel_cast_f32_to_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "carel_rmsprop_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_void_p]),

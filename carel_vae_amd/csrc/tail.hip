@@ -687,15 +687,26 @@ extern "C" int carel_tail_latents(const carel_tail_args* a, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   int rc = tail_check(a, "carel_tail_latents");
   if (rc) return rc;
-  PtrSet4 pp; for (int i = 0; i < 4; ++i) { pp.w[i] = nullptr; pp.b[i] = nullptr; }
-  pp.w[0] = (const float*)a->pooler_w; pp.b[0] = (const float*)a->pooler_b;
   auto sample_groups = [&](int ncols) { int g = (4096 + ncols - 1) / ncols;      /* ~4 k waves: each walks its samples four at a time, one round trip to memory per trip */ const int mx = (a->batch + 3) / 4; g = g > mx ? mx : g; return g < 1 ? 1 : g; };
-  hipLaunchKernelGGL(rowvec_linear_kernel<1>, dim3(TH / 4, sample_groups(TH)), dim3(256), 0, stream, (const float*)a->x_last_f32,
-                     (long)a->seq_len * TH, (const int*)a->cls_rows, a->batch, TH, TH, pp, (float*)a->pooled, (long)TH);
-  PtrSet4 hp; for (int i = 0; i < 4; ++i) { hp.w[i] = (const float*)a->head_w[i]; hp.b[i] = (const float*)a->head_b[i]; }
   const int N = 4 * a->ec_dim;
-  hipLaunchKernelGGL(rowvec_linear_kernel<0>, dim3((N + 3) / 4, sample_groups(N)), dim3(256), 0, stream, (const float*)a->pooled, (long)TH,
-                     (const int*)nullptr, a->batch, N, a->ec_dim, hp, (float*)a->lat, (long)N);
+  if (a->head_in_f32) {      // sentence adapters: the emotion heads read block 0, the cause heads block 1 (no pooler)
+    const int N2 = 2 * a->ec_dim;
+    for (int side = 0; side < 2; ++side) {
+      PtrSet4 hp; for (int i = 0; i < 4; ++i) { hp.w[i] = nullptr; hp.b[i] = nullptr; }
+      for (int i = 0; i < 2; ++i) { hp.w[i] = (const float*)a->head_w[2 * side + i]; hp.b[i] = (const float*)a->head_b[2 * side + i]; }
+      hipLaunchKernelGGL(rowvec_linear_kernel<0>, dim3((N2 + 3) / 4, sample_groups(N2)), dim3(256), 0, stream,
+                         (const float*)a->head_in_f32 + (long)side * a->batch * TH, (long)TH, (const int*)nullptr, a->batch, N2, a->ec_dim, hp,
+                         (float*)a->lat + side * N2, (long)N);
+    }
+  } else {
+    PtrSet4 pp; for (int i = 0; i < 4; ++i) { pp.w[i] = nullptr; pp.b[i] = nullptr; }
+    pp.w[0] = (const float*)a->pooler_w; pp.b[0] = (const float*)a->pooler_b;
+    hipLaunchKernelGGL(rowvec_linear_kernel<1>, dim3(TH / 4, sample_groups(TH)), dim3(256), 0, stream, (const float*)a->x_last_f32,
+                       (long)a->seq_len * TH, (const int*)a->cls_rows, a->batch, TH, TH, pp, (float*)a->pooled, (long)TH);
+    PtrSet4 hp; for (int i = 0; i < 4; ++i) { hp.w[i] = (const float*)a->head_w[i]; hp.b[i] = (const float*)a->head_b[i]; }
+    hipLaunchKernelGGL(rowvec_linear_kernel<0>, dim3((N + 3) / 4, sample_groups(N)), dim3(256), 0, stream, (const float*)a->pooled, (long)TH,
+                       (const int*)nullptr, a->batch, N, a->ec_dim, hp, (float*)a->lat, (long)N);
+  }
   if (a->eps_e && a->eps_c && a->z)      // the sampled embeddings, for callers that exchange them before carel_tail_losses (data parallel)
     hipLaunchKernelGGL(sample_z_kernel, dim3((a->batch * 2 * a->ec_dim + 255) / 256), dim3(256), 0, stream, (const float*)a->lat,
                        (const float*)a->eps_e, (const float*)a->eps_c, a->batch, a->ec_dim, (float*)a->z);
@@ -925,13 +936,33 @@ extern "C" int carel_tail_backward_dz(const carel_tail_args* a, const void* grad
     hipLaunchKernelGGL(tail_add_dz_kernel, dim3((B * 2 * D + 255) / 256), dim3(256), 0, stream, (const float*)dz_extra, (const float*)a->lat,
                        (const float*)a->eps_e, (const float*)a->eps_c, B, D, w.dlat);
   }
+  const int hc = (N + DG_CHUNK - 1) / DG_CHUNK, pc = (TH + DG_CHUNK - 1) / DG_CHUNK;
+  const long bt = (long)B * TH;
+  if (a->head_in_f32) {      // sentence adapters: d head_in per side; the pooler is unused (zero gradient), dx_last is carel_adapter_backward's
+    if (!a->d_head_in_f32) return set_error(CAREL_ERR_ARG, "carel_tail_backward: head_in_f32 needs d_head_in_f32");
+    const int N2 = 2 * D, hc2 = (N2 + DG_CHUNK - 1) / DG_CHUNK;
+    for (int side = 0; side < 2; ++side) {
+      PtrSet4 hp; OutSet4 ho;
+      for (int i = 0; i < 4; ++i) { hp.w[i] = nullptr; hp.b[i] = nullptr; ho.w[i] = nullptr; ho.b[i] = nullptr; }
+      for (int i = 0; i < 2; ++i) { hp.w[i] = (const float*)a->head_w[2 * side + i]; ho.w[i] = (float*)a->d_head_w[2 * side + i]; ho.b[i] = (float*)a->d_head_b[2 * side + i]; }
+      const float* hin = (const float*)a->head_in_f32 + side * bt;
+      if (ho.w[0] && ho.w[1])
+        hipLaunchKernelGGL(rowvec_wgrad_kernel, dim3((N2 + 3) / 4), dim3(256), 0, stream, (const float*)w.dlat + side * N2, (long)N, hin,
+                           (long)TH, (const int*)nullptr, B, N2, D, ho);
+      hipLaunchKernelGGL(rowvec_dgrad_kernel<0>, dim3((B + 3) / 4, hc2), dim3(256), 0, stream, (const float*)w.dlat + side * N2, (long)N, B, N2, D, hp,
+                         (const float*)nullptr, (float*)nullptr, w.dgpart);
+      hipLaunchKernelGGL(sum_parts_kernel, dim3((unsigned)((bt / 4 + 255) / 256)), dim3(256), 0, stream, (const float*)w.dgpart,
+                         (float*)a->d_head_in_f32 + side * bt, bt, hc2);
+    }
+    (void)hipMemsetAsync(a->d_pooler_w, 0, (size_t)TH * TH * sizeof(float), stream);
+    (void)hipMemsetAsync(a->d_pooler_b, 0, (size_t)TH * sizeof(float), stream);
+    return check_launch("tail backward (adapter heads)");
+  }
   PtrSet4 hp; OutSet4 ho;
   for (int i = 0; i < 4; ++i) { hp.w[i] = (const float*)a->head_w[i]; hp.b[i] = nullptr; ho.w[i] = (float*)a->d_head_w[i]; ho.b[i] = (float*)a->d_head_b[i]; }
   if (ho.w[0] && ho.w[1] && ho.w[2] && ho.w[3])
     hipLaunchKernelGGL(rowvec_wgrad_kernel, dim3((N + 3) / 4), dim3(256), 0, stream, (const float*)w.dlat, (long)N, (const float*)a->pooled,
                        (long)TH, (const int*)nullptr, B, N, D, ho);
-  const int hc = (N + DG_CHUNK - 1) / DG_CHUNK, pc = (TH + DG_CHUNK - 1) / DG_CHUNK;
-  const long bt = (long)B * TH;
   hipLaunchKernelGGL(rowvec_dgrad_kernel<0>, dim3((B + 3) / 4, hc), dim3(256), 0, stream, (const float*)w.dlat, (long)N, B, N, D, hp,
                      (const float*)nullptr, (float*)nullptr, w.dgpart);
   hipLaunchKernelGGL(sum_parts_kernel, dim3((unsigned)((bt / 4 + 255) / 256)), dim3(256), 0, stream, (const float*)w.dgpart, w.dpooled, bt, hc);

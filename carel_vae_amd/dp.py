@@ -17,6 +17,8 @@ rank * B).
 import torch
 import torch.distributed as dist
 
+from . import _lib as L
+
 
 class _Pending:
     """One bucket's collective.  `wait()` is what a consumer of the averaged gradients calls on ITS stream: it makes
@@ -98,6 +100,8 @@ class DataParallel:
     def __init__(self, model, group=None, global_batch_terms=True, wire_dtype=None, embed_chunks=4, overlap_wgrad=False):
         if not dist.is_initialized():
             raise RuntimeError("torch.distributed must be initialised (init_process_group) before DataParallel")
+        if getattr(model, "adapter", "false") != "false":
+            raise L.CarelError("sentence adapters are not supported under DataParallel")
         self.model, self.group = model, group
         self.rank, self.world = dist.get_rank(group), dist.get_world_size(group)
         self.global_batch_terms = global_batch_terms

@@ -124,6 +124,42 @@ class _Pooler(nn.Module):
         self.dense = _Holder((H, H))
 
 
+class _Adapter(nn.Module):
+    """Parameter holder with the state_dict keys of the EMNLP scripts' sentence adapters (drl_classifier_ec_mmd_final_mul_emnlp.py):
+    nn.MultiheadAttention(768, head_number) for "raw" (:277), and for "sparsemax" / "entmax" its subclasses (:162-256), which add the
+    q_proj / k_proj / v_proj linears -- in_proj_* , out_proj and v_proj exist there but only q_proj and k_proj are used."""
+
+    def __init__(self, sparse):
+        super().__init__()
+        self.in_proj_weight = nn.Parameter(torch.empty(3 * H, H))
+        self.in_proj_bias = nn.Parameter(torch.empty(3 * H))
+        self.out_proj = _Holder((H, H))
+        if sparse:
+            self.q_proj, self.k_proj, self.v_proj = _Holder((H, H)), _Holder((H, H)), _Holder((H, H))
+
+
+ADAPTERS = ("false", "raw", "sparsemax", "entmax")
+
+
+def adapter_config(opt):
+    """(adapter, head_number) of the EMNLP scripts' --adapter / --head_number (:61-63); "false" (or no attribute): the pooler model."""
+    mode = getattr(opt, "adapter", "false")
+    if mode is False or mode is None:
+        mode = "false"
+    heads = getattr(opt, "head_number", 4)
+    if mode not in ADAPTERS:
+        raise L.CarelError("opt.adapter must be one of %s; got %r" % (", ".join(ADAPTERS), mode))
+    if mode == "false":
+        return mode, heads
+    if int(heads) != heads or heads < 1 or H % int(heads):
+        raise L.CarelError("opt.head_number must divide 768 (nn.MultiheadAttention); got %r" % (heads,))
+    if mode == "raw" and heads > 12:
+        raise L.CarelError("the raw adapter kernels support head_number <= 12; got %d" % heads)
+    if getattr(opt, "disentangle", "mmd") != "mmd":
+        raise L.CarelError("sentence adapters exist in the MMD scripts only (opt.disentangle must be 'mmd')")
+    return mode, int(heads)
+
+
 class CarelEncoder(nn.Module):
     """Parameter container with the key names of transformers BertModel / RobertaModel."""
 
@@ -147,6 +183,16 @@ def _init_like_reference(model, gen=None):
                     p.zero_()
                 else:
                     p.normal_(0.0, 0.02, generator=gen)
+            elif "_adapter." in name:       # nn.MultiheadAttention._reset_parameters: xavier in_proj, zero biases; the rest nn.Linear's
+                leaf = name.split("_adapter.", 1)[1]
+                if leaf == "in_proj_weight":
+                    bound = math.sqrt(6.0 / (p.shape[0] + p.shape[1]))
+                    p.uniform_(-bound, bound, generator=gen)
+                elif leaf in ("in_proj_bias", "out_proj.bias"):
+                    p.zero_()
+                else:
+                    bound = 1.0 / math.sqrt(H)
+                    p.uniform_(-bound, bound, generator=gen)
             elif name.endswith(".weight"):
                 bound = 1.0 / math.sqrt(p.shape[1])
                 p.uniform_(-bound, bound, generator=gen)
@@ -331,8 +377,10 @@ class DrlClassifier(nn.Module):
         self.cfg = encoder_cfg if encoder_cfg is not None else encoder_config(getattr(opt, "language", "zh"))
         if opt.bert_dim != H:
             raise L.CarelError("bert_dim must be 768 (BERT-base kernels)")
+        self.adapter, self.head_number = adapter_config(opt)
         self.encoder = CarelEncoder(self.cfg)
         self._aprx_names = []
+        self._adapter_names = []
         self._has_pair_skip = True          # the pair head is frozen for a step whose pair loss was replaced by 0 (ref :510-511)
         self.strict_pair_skip = False       # True: also leave its .grad None on such a step (for stock torch optimisers; one host read per step)
         self._build_heads(opt)
@@ -340,6 +388,10 @@ class DrlClassifier(nn.Module):
         if seed is not None:
             gen = torch.Generator().manual_seed(seed)
         _init_like_reference(self, gen)
+        if self.adapter != "false":
+            # fixed queries (:275, :284): not parameters, not in the state_dict; drawn from the model's generator, assignable
+            self.register_buffer("emotion_q", torch.randn(1, 1, H, generator=gen), persistent=False)
+            self.register_buffer("cause_q", torch.randn(1, 1, H, generator=gen), persistent=False)
         self.dropout_base_seed = 0x5EED
         self.varlen = True                   # skip padded positions (results identical; see _pack_info)
         self.cls_only_last = True            # last layer's row-wise half on the [CLS] rows only (results identical)
@@ -358,6 +410,11 @@ class DrlClassifier(nn.Module):
         self._flatten()
 
     def _build_heads(self, opt):
+        if self.adapter != "false":         # registered where the reference builds them (:273-291): before the latent heads
+            self.emotion_adapter = _Adapter(self.adapter != "raw")
+            self.cause_adapter = _Adapter(self.adapter != "raw")
+            self._adapter_names = ["%s_adapter.%s" % (side, n) for side in ("emotion", "cause")
+                                   for n, _ in getattr(self, side + "_adapter").named_parameters()]
         self.emotion_mu = _Holder((opt.ec_dim, H))
         self.emotion_log_var = _Holder((opt.ec_dim, H))
         self.cause_mu = _Holder((opt.ec_dim, H))
@@ -385,6 +442,7 @@ class DrlClassifier(nn.Module):
         n_opt_names = len(order)
         order += ["emotion_mu.weight", "emotion_mu.bias", "emotion_log_var.weight", "emotion_log_var.bias",
                   "cause_mu.weight", "cause_mu.bias", "cause_log_var.weight", "cause_log_var.bias"]
+        order += self._adapter_names         # frozen like the latent heads (absent from get_params() in the reference, :460)
         order += self._aprx_names            # own optimiser (ref ec_vi :873), fp32 only
         assert set(order) == set(named), "parameter inventory mismatch"
         return order, n_opt_names, named
@@ -584,7 +642,7 @@ class DrlClassifier(nn.Module):
     def _cls_info(self, B, Bp, S, pack, dev):
         """Index arrays of the dead-row elimination (include/carel_hip.h, carel_encoder_args.n_cls); B real samples,
         Bp = batch the encoder runs (padded so that Bp*S is a multiple of 128)."""
-        if not self.cls_only_last:
+        if not self.cls_only_last or self.adapter != "false":        # an adapter reads every row of the last layer
             return None
         n_cls = (Bp + 127) // 128 * 128
         key = ("cls", B, Bp, S)
@@ -677,8 +735,9 @@ class DrlClassifier(nn.Module):
         pair to max_len and ~77 % of ECPE tokens are padding).  Exact for prefix-form masks (HF right padding): padded
         positions are never attended to and nothing but [CLS] is read from the last layer, so every output and
         gradient is unchanged; dropout masks and position ids keep using the ORIGINAL (sample, position) index.
-        Returns None to run dense (no padding in the batch, non-prefix mask, or varlen disabled)."""
-        if not self.varlen or att is None:
+        Returns None to run dense (no padding in the batch, non-prefix mask, or varlen disabled; always with a sentence adapter, which
+        attends to the padded positions too)."""
+        if not self.varlen or att is None or self.adapter != "false":
             return None
         if seq_lengths is None:
             m = att[:B].to(torch.int32)
@@ -748,6 +807,8 @@ class DrlClassifier(nn.Module):
         c.seed = (self.dropout_base_seed * 1000003 + self._fwd_count) & 0xFFFFFFFF
         c.row_offset = 0 if self._dp is None else self._dp.row_offset(B)
         c.pack = self._pack_info(c.att, B, Bp, S, seq_lengths)
+        if self.adapter != "false" and self._dp is not None:
+            raise L.CarelError("sentence adapters are not supported under DataParallel")
         key = ("tail", B, S)
         buf = self._ws.get(key)
         if buf is None:
@@ -768,6 +829,39 @@ class DrlClassifier(nn.Module):
         p = self._named[k]
         o = self._offs[k]
         return self._flat_grad[o:o + p.numel()].view(p.shape)
+
+    # ------------------------------------------------------------------ sentence adapters (EMNLP scripts)
+    def _adapter_weights(self):
+        out = []
+        for side in ("emotion", "cause"):
+            m = getattr(self, side + "_adapter")
+            if self.adapter == "raw":
+                w, b = m.in_proj_weight.data, m.in_proj_bias.data
+                out.append(dict(q_w=w[:H], q_b=b[:H], k_w=w[H:2 * H], v_w=w[2 * H:], v_b=b[2 * H:], o_w=m.out_proj.weight.data,
+                                o_b=m.out_proj.bias.data))
+            else:
+                out.append(dict(q_w=m.q_proj.weight.data, q_b=m.q_proj.bias.data, k_w=m.k_proj.weight.data))
+        return out
+
+    def _adapter_forward(self, c, x_last_ptr):
+        """Adapter outputs [2, B, 768] from the dense last hidden states.  u is rebuilt on every call (a few microseconds), so a change
+        of the queries or adapter weights by any route -- load_state_dict, an in-place edit, a write through .data -- takes effect."""
+        dev = self._flat.device
+        G = self.head_number if self.adapter == "raw" else 1
+        key = ("adapter", c.B, c.S)
+        buf = self._ws.get(key)
+        if buf is None:
+            buf = self._ws[key] = ops.AdapterBuffers(c.B, c.S, G, dev)
+        qs = [getattr(self, n).to(dev, torch.float32).reshape(-1).contiguous() for n in ("emotion_q", "cause_q")]
+        if qs[0].numel() != H or qs[1].numel() != H:
+            raise L.CarelError("emotion_q / cause_q must hold 768 values")
+        u = self._ws.get("adapter_u")
+        if u is None:
+            u = self._ws["adapter_u"] = torch.empty((2, G, H), device=dev, dtype=torch.float32)
+        a = ops.adapter_args(self.adapter, G, qs, self._adapter_weights(), u, buf, c.Bp, x=SimpleNamespace(data_ptr=lambda: x_last_ptr))
+        ops.adapter_build_u(a)
+        ops.adapter_forward(a)
+        return a, buf
 
     def _run_forward(self, c, training):
         if self._adam_hook is not None:
@@ -791,13 +885,19 @@ class DrlClassifier(nn.Module):
             x_last_ptr = lib.carel_encoder_x_last(C.byref(ea))
         W, G = self._tail_weights()
         xl = SimpleNamespace(data_ptr=lambda: x_last_ptr)
+        c.ad = None
+        head_in = d_head_in = None
+        if self.adapter != "false":
+            c.ad, abuf = self._adapter_forward(c, x_last_ptr)
+            head_in, d_head_in = abuf.out, abuf.d_out
         klw = ops.kl_anneal_weight(c.iteration, self.opt)
         drop = (self.opt.dropout if train_drop else 0.0, c.seed, c.row_offset)
         if c.cls is not None:           # compact final hidden states: sample i's [CLS] is row i
             cls_rows, n_rows = c.cls.compact, c.cls.n_cls
         else:
             cls_rows, n_rows = (None, c.Bp * c.S) if c.pack is None else (c.pack.cu, c.pack.n_tokens)
-        ta = ops.tail_args(c.buf, xl, W, c.labels, c.eps_e, c.eps_c, self.opt, klw, grads=G, drop=drop, cls_rows=cls_rows, n_rows=n_rows)
+        ta = ops.tail_args(c.buf, xl, W, c.labels, c.eps_e, c.eps_c, self.opt, klw, grads=G, drop=drop, cls_rows=cls_rows, n_rows=n_rows,
+                           head_in=head_in, d_head_in=d_head_in)
         ops.tail_latents(ta)
         if self._dp is not None:
             self._dp.fill_global(ta, c)                  # all-gather z, all-reduce label sum
@@ -817,12 +917,22 @@ class DrlClassifier(nn.Module):
         ea = c.ea
         ea.dx = c.buf.dx_last.data_ptr()          # [Bp*S (or packed n_tokens), 768]; cleared + CLS rows written by the tail backward
         ops.tail_backward(c.ta, go, None if grad_z is None else grad_z.to(torch.float32).contiguous())
+        if c.ad is not None:                     # adapter mode: d head_in -> every row of dx_last (the tail left dx_last alone)
+            c.ad.dx_f32 = ea.dx
+            ops.adapter_backward(c.ad)
         # classifier / decoder gradients were produced for grad_output = 1: one contiguous range of the flat buffer
         lo = self._offs["decoder.weight"]
         ops.scale_(self._flat_grad[lo:self._pair_hi], go)
         if self._dp is not None:
             self._dp.tail_done()
         self._backward_encoder(ea, accumulate)
+        if c.ad is not None:
+            # the adapters read padded positions, so for once they carry gradient; HF's embeddings have padding_idx = pad_id (word table,
+            # and RoBERTa's position table, whose padded positions take position pad_id): that row gets none
+            e = "encoder.embeddings."
+            self._grad_view(e + "word_embeddings.weight")[self.cfg.pad_id].zero_()
+            if self.cfg.roberta:
+                self._grad_view(e + "position_embeddings.weight")[self.cfg.pad_id].zero_()
         if self._dp is not None:
             self._dp.backward_done(None if accumulate else self._adam_hook)
         if accumulate:
@@ -867,9 +977,9 @@ class DrlClassifier(nn.Module):
     def _bind_grads(self):
         if self._grad_views is None:
             self._grad_views = {k: self._grad_view(k) for k in self._order}
-        aprx = self._aprx_names
+        skip = set(self._aprx_names) | set(self._adapter_names)
         for k, p in self._named.items():
-            if k not in aprx:               # the approximation net's gradients belong to _AprxLoss.backward
+            if k not in skip:               # the approximation net's gradients belong to _AprxLoss.backward; adapters get none (frozen)
                 p.grad = self._grad_views[k]
 
     # ------------------------------------------------------------------ public API (reference surface)
@@ -914,8 +1024,12 @@ class DrlClassifier(nn.Module):
         D = self.opt.ec_dim
         lat = c.buf.lat.clone()
         out = {n: t[i] for i, n in enumerate(self.TERM_NAMES)}
-        out.update(mu_e=lat[:, :D], lv_e=lat[:, D:2 * D], mu_c=lat[:, 2 * D:3 * D], lv_c=lat[:, 3 * D:], pooled=c.buf.pooled.clone(),
-                   z=c.buf.z.clone())
+        out.update(mu_e=lat[:, :D], lv_e=lat[:, D:2 * D], mu_c=lat[:, 2 * D:3 * D], lv_c=lat[:, 3 * D:], z=c.buf.z.clone())
+        if c.ad is not None:                 # the heads' inputs: emotion / cause adapter outputs (the pooler is not run)
+            a = self._ws[("adapter", c.B, c.S)].out
+            out.update(adapter_e=a[0].clone(), adapter_c=a[1].clone())
+        else:
+            out.update(pooled=c.buf.pooled.clone())
         return out
 
     def last_terms(self):
@@ -954,8 +1068,12 @@ class DrlClassifier(nn.Module):
                 buf = ops.TailBuffers(B, S, self.opt.ec_dim, self.opt.e_num_class, self.opt.pair_bow_dim, dev, rows=Bp * S)
                 self._ws[key] = buf
             W, _ = self._tail_weights()
+            head_in = None
+            if self.adapter != "false":
+                _, abuf = self._adapter_forward(SimpleNamespace(B=B, Bp=Bp, S=S), x_last_ptr)
+                head_in = abuf.out
             ta = ops.tail_args(buf, SimpleNamespace(data_ptr=lambda: x_last_ptr), W, None, None, None, self.opt, 1.0,
-                               cls_rows=cls.compact if cls is not None else (None if pack is None else pack.cu))
+                               cls_rows=cls.compact if cls is not None else (None if pack is None else pack.cu), head_in=head_in)
             ta._keep = (pack, cls)
             ops.tail_latents(ta)
             out[s:s + B] = ops.pair_probs(buf.lat, eps_e, eps_c, W["pair_classifier.weight"], W["pair_classifier.bias"], self.opt.ec_dim)

@@ -157,6 +157,8 @@ class DrlClassifier(_Base):
     def __init__(self, opt, encoder_cfg=None, seed=None):
         if encoder_cfg is None:
             encoder_cfg = encoder_config("en")
+        if getattr(opt, "adapter", "false") not in ("false", False, None):
+            raise L.CarelError("drl_classifier_en.py has no sentence adapters (opt.adapter belongs to the EMNLP scripts' model)")
         super().__init__(opt, encoder_cfg=encoder_cfg, seed=seed)
         self._has_pair_skip = False          # this script has no "pair loss replaced by 0" branch (:587-603)
 

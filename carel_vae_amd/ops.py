@@ -135,8 +135,9 @@ class TailBuffers:
 
 def tail_args(buf: TailBuffers, x_last, W, labels, eps_e, eps_c, opt, kl_weight, *, grads=None, drop=(0.0, 0, 0),
               global_label_sum=None, global_n=0, global_row_offset=0, z_global=None, mmd_grad_scale=1.0, global_rank_stride=0, global_label_ranks=0, cls_rows=None,
-              n_rows=0):
-    """W / grads: dicts keyed by the reference's state_dict names (tail part)."""
+              n_rows=0, head_in=None, d_head_in=None):
+    """W / grads: dicts keyed by the reference's state_dict names (tail part).  head_in / d_head_in: f32 [2, B, 768] adapter outputs and
+    their gradient (AdapterBuffers.out / .d_out): the latent heads read them instead of the pooler."""
     a = L.TailArgs()
     a.batch, a.seq_len, a.hidden, a.ec_dim, a.e_classes, a.bow_dim = buf.B, buf.S, H, buf.D, buf.EC, buf.V
     a.x_last_f32 = x_last.data_ptr()
@@ -177,6 +178,8 @@ def tail_args(buf: TailBuffers, x_last, W, labels, eps_e, eps_c, opt, kl_weight,
     a.dx_last_f32 = buf.dx_last.data_ptr()
     a.cls_rows = None if cls_rows is None else cls_rows.data_ptr()
     a.n_rows = n_rows if n_rows else buf.rows
+    a.head_in_f32 = None if head_in is None else head_in.data_ptr()
+    a.d_head_in_f32 = None if d_head_in is None else d_head_in.data_ptr()
     if grads is not None:
         a.d_emo_w, a.d_emo_b = grads["emotion_classifier.weight"].data_ptr(), grads["emotion_classifier.bias"].data_ptr()
         a.d_cau_w, a.d_cau_b = grads["cause_classifier.weight"].data_ptr(), grads["cause_classifier.bias"].data_ptr()
@@ -208,6 +211,50 @@ def tail_backward(a, grad_out=None, dz_extra=None):
     L.check(L.load().carel_tail_backward_dz(C.byref(a), None if grad_out is None else grad_out.data_ptr(),
                                             None if dz_extra is None else dz_extra.data_ptr(), L.current_stream()),
             "carel_tail_backward_dz")
+
+
+ADAPTER_MODES = {"raw": 0, "sparsemax": 1, "entmax": 2}
+
+
+class AdapterBuffers:
+    """Outputs + workspace of the sentence-adapter calls for one (batch, seq_len) shape: out / d_out f32 [2, B, 768] (emotion, cause)."""
+
+    def __init__(self, B, S, heads, device):
+        f = dict(device=device, dtype=torch.float32)
+        self.B, self.S, self.heads = B, S, heads
+        self.out = torch.empty((2, B, H), **f)
+        self.d_out = torch.empty((2, B, H), **f)
+        self.work = torch.empty(L.load().carel_adapter_workspace_floats(B, S, heads), **f)
+
+
+def adapter_args(mode, heads, queries, weights, u, buf, Bp, x=None, dx=None):
+    """mode: "raw" / "sparsemax" / "entmax"; queries: two f32 [768] device tensors (emotion, cause); weights: two dicts with q_w, q_b,
+    k_w and (raw) v_w, v_b, o_w, o_b (contiguous f32); u: f32 [2, heads, 768]; buf: AdapterBuffers; x / dx: f32 [Bp*S, 768] (tensor or
+    anything with data_ptr())."""
+    a = L.AdapterArgs()
+    a.batch, a.batch_padded, a.seq_len, a.mode, a.heads = buf.B, Bp, buf.S, ADAPTER_MODES[mode], heads
+    for i in range(2):
+        a.query[i] = queries[i].data_ptr()
+        for f in ("q_w", "q_b", "k_w", "v_w", "v_b", "o_w", "o_b"):
+            t = weights[i].get(f)
+            getattr(a, f)[i] = None if t is None else t.data_ptr()
+    a.u, a.work, a.out_f32, a.d_out_f32 = u.data_ptr(), buf.work.data_ptr(), buf.out.data_ptr(), buf.d_out.data_ptr()
+    a.x_f32 = None if x is None else x.data_ptr()
+    a.dx_f32 = None if dx is None else dx.data_ptr()
+    a._keep = (queries, weights)
+    return a
+
+
+def adapter_build_u(a):
+    L.check(L.load().carel_adapter_build_u(C.byref(a), L.current_stream()), "carel_adapter_build_u")
+
+
+def adapter_forward(a):
+    L.check(L.load().carel_adapter_forward(C.byref(a), L.current_stream()), "carel_adapter_forward")
+
+
+def adapter_backward(a):
+    L.check(L.load().carel_adapter_backward(C.byref(a), L.current_stream()), "carel_adapter_backward")
 
 
 def _vi_args(z, net):

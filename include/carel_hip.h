@@ -32,7 +32,7 @@ extern "C" {
 #define CAREL_ERR_HIP (-3)    /* a HIP runtime call or launch failed    */
 
 /* ABI version of this header; carel_abi_version() must return the same number. */
-#define CAREL_ABI_VERSION 7
+#define CAREL_ABI_VERSION 8
 
 int carel_abi_version(void);
 /* Checks that `device` is a gfx950 part and fills the library's only per-device state, immutable afterwards: the 20-KiB GELU table of
@@ -423,6 +423,15 @@ typedef struct carel_tail_args {
                                         (carel_side_stream(0)) beside the decoder passes on `stream`, forked and joined with events inside
                                         the call -- `stream` order is all a caller ever sees; 1: every kernel on `stream`, in order
                                         (serial kernel traces, per-launch timing) */
+  /* ABI 8: the sentence adapters of drl_classifier_ec_mmd_final_mul_emnlp.py (:334-354; carel_adapter_* below).  NULL (default):
+   * the pooler path above, unchanged.  Set: the latent heads read these rows instead of the pooler --
+   *   head_in_f32   f32 [2, B, 768]: block 0 = emotion adapter output (read by emotion_mu / emotion_log_var),
+   *                 block 1 = cause adapter output (cause_mu / cause_log_var); carel_tail_latents skips the pooler (`pooled` unwritten);
+   *   d_head_in_f32 f32 [2, B, 768]: carel_tail_backward writes d loss / d head_in here (scaled by grad_out) instead of running the
+   *                 pooler backward and the [CLS] scatter; dx_last_f32 is left to carel_adapter_backward, and d_pooler_w / d_pooler_b
+   *                 (when given) are zero-filled -- the pooler is unused (its gradient is None in the reference). */
+  const void* head_in_f32;
+  void* d_head_in_f32;
 } carel_tail_args;
 
 int64_t carel_tail_workspace_floats(int32_t batch, int32_t ec_dim, int32_t bow_dim);
@@ -471,6 +480,55 @@ int carel_scale_f32(void* x_f32, int64_t n, const void* scale_dev_f32, void* str
 int64_t carel_tail_pair_dead_offset(int32_t batch, int32_t ec_dim, int32_t bow_dim);
 int carel_pair_probs(const void* lat, const void* eps_e, const void* eps_c, const void* pair_w, const void* pair_b,
                      int32_t batch, int32_t ec_dim, void* prob, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Sentence adapters (ABI 8) of drl_classifier_ec_mmd_final_mul_emnlp.py / ..._newsplit_emnlp.py: the emotion and the cause latent
+ * branches each read their own attention adapter over EVERY position of the last hidden state H [B, S, 768] (:334-354, get_pair_preds
+ * :420-442) instead of the pooler.  A fixed query e (emotion_q / cause_q, :275 / :284) attends over all S positions; no mask, so
+ * padded positions are attended too.
+ *   mode 1 sparsemax (SparsemaxMultiheadAttention, :162-210), mode 2 entmax15 (EntmaxMultiheadAttention, :213-256), G = 1:
+ *       scores[b,s] = q_proj(e) . k_proj(H[b,s]) / sqrt(768);  p = normaliser(scores[b,:]);  out[b] = sum_s p[b,s] H[b,s]
+ *       (value = the raw H; v_proj, in_proj_* and out_proj exist but are unused there);
+ *   mode 0 raw (nn.MultiheadAttention(768, G, batch_first=True) called as (e, H, H), :277 / :286), G = head_number:
+ *       per head h: softmax(q_h . k_h(H) / sqrt(768/G)), v = in_proj_v(H), then out_proj.
+ * Every normaliser is translation-invariant, so the key bias drops out and the key projection reassociates exactly:
+ *   u_h = W_k,h^T q_h / sqrt(d)  (carel_adapter_build_u),  scores_h[b,s] = H[b,s] . u_h
+ * -- no [B*S, 768] x [768, 768] GEMM.  For raw mode the value projection and out_proj act after the weighted sum (sum_s p = 1).
+ * Both adapters go through one pass over H.  f32 throughout; exact sort-based normalisers (ties included); no atomics (results
+ * are bitwise repeatable).  seq_len in {32, 64, 96, 128}; G | 768, G <= 12; G = 1 for modes 1 / 2.
+ *
+ * Weights per adapter a (0 = emotion, 1 = cause), each [768, 768] row-major (nn.Linear layout) / [768]:
+ *   modes 1 / 2: q_w / q_b = q_proj, k_w = k_proj.weight;   v_* / o_* unused (may be NULL)
+ *   mode 0:      q_w / q_b = in_proj rows 0..767, k_w = in_proj rows 768..1535, v_w / v_b = in_proj rows 1536..2303, o_w / o_b = out_proj
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct carel_adapter_args {
+  int32_t batch;                     /* B real samples */
+  int32_t batch_padded;              /* Bp >= B: samples (of seq_len rows each) in x / dx; the filler samples' dx rows are written 0 */
+  int32_t seq_len;                   /* S */
+  int32_t mode;                      /* 0 raw (softmax), 1 sparsemax, 2 entmax15 */
+  int32_t heads;                     /* G query vectors per adapter */
+  const void* query[2];              /* f32 [768]: emotion_q, cause_q */
+  const void* q_w[2]; const void* q_b[2];
+  const void* k_w[2];
+  const void* v_w[2]; const void* v_b[2];
+  const void* o_w[2]; const void* o_b[2];
+  void* u;                           /* f32 [2, G, 768]: written by carel_adapter_build_u, read by forward and backward */
+  const void* x_f32;                 /* f32 [Bp*S, 768] last hidden states (carel_encoder_x_last, dense rows) */
+  void* out_f32;                     /* f32 [2, B, 768] adapter outputs (= carel_tail_args.head_in_f32) */
+  const void* d_out_f32;             /* f32 [2, B, 768] (backward; = carel_tail_args.d_head_in_f32) */
+  void* dx_f32;                      /* f32 [Bp*S, 768] (backward): d loss / d H, every row written (the encoder backward's dx) */
+  void* work;                        /* f32 [carel_adapter_workspace_floats(B, S, G)]; the forward leaves p there for the backward */
+} carel_adapter_args;
+int64_t carel_adapter_workspace_floats(int32_t batch, int32_t seq_len, int32_t heads);
+/* u from query / q_* / k_w (a GEMV and a transposed GEMV per adapter).  Call whenever the queries or those weights changed. */
+int carel_adapter_build_u(const carel_adapter_args* args, void* stream);
+/* out (and p in work) from x and u */
+int carel_adapter_forward(const carel_adapter_args* args, void* stream);
+/* dx from d_out, x, u and the p of the preceding forward:  dctx = d_out (modes 1 / 2) or W_v,h^T (W_o^T d_out)_h (raw);
+ * dp[h,s] = H_s . dctx_h;  dz = normaliser backward (softmax p(dp - sum p dp); sparsemax dp - mean_support dp on p > 0;
+ * entmax15 g dp - (sum g dp / sum g) g with g = sqrt(p));  dH_s = sum_adapters sum_h p[h,s] dctx_h + dz[h,s] u_h.
+ * Adapter weight gradients are not formed (the reference never applies them: its get_params() leaves the adapters out, :460). */
+int carel_adapter_backward(const carel_adapter_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Fused Adam over a flat parameter buffer.  Replaces torch.optim.Adam(...).step() (ref :936, :842) with
