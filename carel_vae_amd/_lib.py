@@ -296,6 +296,8 @@ EXP_SIGNATURES = {
     "carel_gemm_set_variant": (C.c_int, [C.c_int32]),
     "carel_gemm_rowln": (C.c_int, [C.POINTER(GemmRowLnArgs), C.c_void_p]),
     "carel_gemm_rowln_pack": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "carel_gemm_split_plan": (C.c_int, [C.POINTER(GemmArgs), C.c_int32, C.POINTER(C.c_int32)]),
+    "carel_encoder_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
 }
 EXP_LIB_PATH = os.path.join(_HERE, "libcarel_hip_exp.so")
 

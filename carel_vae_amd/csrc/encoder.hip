@@ -219,6 +219,12 @@ int wgrad_call(const void* dY, const void* X, long T, int M, int N, void* slabs,
 }  // namespace
 
 #ifdef CAREL_EXPERIMENTS
+// the byte counts the encoder hands its GEMMs for a batch x seq_len scratch block: which = 0 the split-K workspace of the forward / data-gradient
+// GEMMs, 1 the weight-gradient slab area (the grouped launch runs when its workspace fits there)
+extern "C" int64_t carel_encoder_workspace_bytes(int32_t batch, int32_t seq_len, int32_t which) {
+  const ScratchLayout sl = scratch_layout(batch, seq_len);
+  return which == 0 ? (int64_t)sl.ws_bytes : which == 1 ? (int64_t)sl.slab_bytes : -1;
+}
 namespace carel { void encoder_ln_resid_enable(int on) { g_ln_resid = on ? 1 : 0; } void encoder_wgrad_group_enable(int on) { g_wgrad_group = on ? 1 : 0; }
                   void encoder_ln_slab_fusion_enable(int on) { g_ln_slab_fusion = on ? 1 : 0; } }
 #endif

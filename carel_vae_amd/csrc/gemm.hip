@@ -485,20 +485,52 @@ static int sm_plan(const GemmParams& p, int epi, bool at) {
   return s;
 }
 
-static thread_local int tl_split_plan = 1;      // result of the last GEMM_EX_PLAN_ONLY pass (gemm_bf16_split_plan)
+// K slices of an internally split row-major-A GEMM on the ping-pong kernel: its npn where the tiles x slices fit one round, 0 = the 128x128 kernel
+// (packed ECPE batches, ~1.8 k rows: 56 tiles x 4 slices of 12 K tiles each run in ~13 us against ~20 us for 84 x 4 workgroups of the 128x128
+// kernel with its barrier + vmcnt(0) per K step); same K partition, same order of additions inside a slice: the same bits (tests/test_gpu_gemm.py)
+static int split_pp_npn(const GemmParams& p, bool at, int sp) {
+  if (at || !g_pp_split || p.N % 96 || p.M <= 128 || (p.K / sp) % 64 || p.K / sp < 256) return 0;
+  const long t1 = (long)((p.M + 255) / 256) * (p.N / 96) * sp;
+  if (t1 <= 256) return 1;
+  if (p.N % 192 == 0 && t1 / 2 <= 256) return 2;
+  return 0;
+}
+
+// result of the last GEMM_EX_PLAN_ONLY pass (gemm_bf16_split_plan): slabs, kernel family (CAREL_PLAN_*, include/carel_hip_experiments.h), npn
+static thread_local int tl_split_plan = 1, tl_plan_family = 0, tl_plan_npn = 0;
+enum { PLAN_PP = 1, PLAN_128 = 2, PLAN_BIG = 3, PLAN_PP_SLABS = 4, PLAN_128_SLABS = 5, PLAN_SM = 6 };
+#ifdef CAREL_EXPERIMENTS
+static_assert(PLAN_PP == CAREL_PLAN_PP && PLAN_128 == CAREL_PLAN_128 && PLAN_BIG == CAREL_PLAN_BIG && PLAN_PP_SLABS == CAREL_PLAN_PP_SLABS &&
+              PLAN_128_SLABS == CAREL_PLAN_128_SLABS && PLAN_SM == CAREL_PLAN_SM && CAREL_PLAN_FIXED_ROWS == GEMM_EX_FIXED_ROWS, "plan codes");
+#endif
 template <bool AT, bool BT, int EPI>
 static int launch(const GemmParams& p, int splits, hipStream_t s) {
   const bool plan_only = (p.split_tile_factor & GEMM_EX_PLAN_ONLY) != 0, defer = (p.split_tile_factor & GEMM_EX_DEFER_EPILOGUE) != 0;
-  if (plan_only) {          // the decisions below without a launch: does this call take the internal split-K path, and with how many slabs?
-    tl_split_plan = 1;
-    if (const int sms = sm_plan(p, EPI, AT)) { tl_split_plan = sms; return CAREL_OK; }
+  if (plan_only) {          // the decisions below without a launch: which kernel, does this call take the internal split-K path, with how many slabs?
+    tl_split_plan = 1; tl_plan_family = 0; tl_plan_npn = 0;
+    if (const int sms = sm_plan(p, EPI, AT)) { tl_split_plan = sms; tl_plan_family = PLAN_SM; return CAREL_OK; }
+    const bool big_ok = (p.M % 256 == 0) && (p.N % 192 == 0), v1_ok = (p.M % 128 == 0) && (p.N % 128 == 0);
+    int rs = 1;
     if (!AT && g_gemm_variant == 0) {
       const bool only_pp = !((p.M % 128 == 0 && p.N % 128 == 0) || (p.M % 256 == 0 && p.N % 192 == 0));
-      if (resid_split(p, EPI) > 1) { tl_split_plan = resid_split(p, EPI); return CAREL_OK; }
-      if (gemm_pp_pick(p, BT, EPI, only_pp ? 1 : -(p.K <= 768 ? g_pp_min_tiles_k768 : g_pp_min_tiles))) return CAREL_OK;
-      const bool big_ok = (p.M % 256 == 0) && (p.N % 192 == 0), v1_ok = (p.M % 128 == 0) && (p.N % 128 == 0);
-      if ((big_ok && !v1_ok) || !v1_ok) return CAREL_OK;
-      if (EPI != EPI_SLAB_F32 && p.splitk_ws) tl_split_plan = auto_splits(p, p.splitk_ws_bytes);
+      rs = resid_split(p, EPI);
+      if (rs <= 1) {
+        if (const int npn = gemm_pp_pick(p, BT, EPI, only_pp ? 1 : -(p.K <= 768 ? g_pp_min_tiles_k768 : g_pp_min_tiles))) {
+          tl_plan_family = PLAN_PP; tl_plan_npn = npn;
+          return CAREL_OK;
+        }
+      }
+    } else if (!AT) {
+      return CAREL_OK;      // (tuning hooks: not planned)
+    }
+    if (big_ok && (!v1_ok || (g_gemm_variant == 0 && big_auto(p, splits)))) { tl_plan_family = PLAN_BIG; return CAREL_OK; }
+    if (!v1_ok) return CAREL_OK;
+    const int sp = (EPI != EPI_SLAB_F32 && p.splitk_ws) ? (rs > 1 ? rs : auto_splits(p, p.splitk_ws_bytes)) : 1;
+    if (sp > 1) {
+      tl_split_plan = sp; tl_plan_npn = split_pp_npn(p, AT, sp);
+      tl_plan_family = tl_plan_npn ? PLAN_PP_SLABS : PLAN_128_SLABS;
+    } else {
+      tl_plan_family = PLAN_128;
     }
     return CAREL_OK;
   }
@@ -563,15 +595,7 @@ static int launch(const GemmParams& p, int splits, hipStream_t s) {
     if (sp > 1) {
       GemmParams q = p;
       q.K = p.K / sp; q.outf = p.splitk_ws; q.ldc = p.N; q.colsum_part = nullptr;
-      // the slices on the ping-pong kernel where its tiles x slices fit one round (packed ECPE batches, ~1.8 k rows: 56 tiles x 4 slices of
-      // 12 K tiles each run in ~13 us against ~20 us for 84 x 4 workgroups of the 128x128 kernel with its barrier + vmcnt(0) per K step);
-      // same K partition, same order of additions inside a slice: the same bits (tests/test_gpu_gemm.py)
-      int pp_npn = 0;
-      if (!AT && g_pp_split && p.N % 96 == 0 && p.M > 128 && (p.K / sp) % 64 == 0 && p.K / sp >= 256) {
-        const long t1 = (long)((p.M + 255) / 256) * (p.N / 96) * sp;
-        if (t1 <= 256) pp_npn = 1;
-        else if (p.N % 192 == 0 && t1 / 2 <= 256) pp_npn = 2;
-      }
+      const int pp_npn = split_pp_npn(p, AT, sp);
       const long chunks = (long)p.M * (p.N >> 3);
       if (pp_npn) {
         q.K = p.K;                       // the ping-pong kernel slices K by gridDim.z itself
@@ -832,6 +856,19 @@ int carel::gemm_bf16_split_plan(const carel_gemm_args* a, int split_tile_factor)
   return tl_split_plan;
 }
 
+#ifdef CAREL_EXPERIMENTS
+// the plan-only pass above with the kernel family and tile width it decided on (tests/test_packed_dispatch.py)
+extern "C" int carel_gemm_split_plan(const carel_gemm_args* a, int32_t flags, int32_t* plan) {
+  if (!plan) return set_error(CAREL_ERR_ARG, "carel_gemm_split_plan: null plan");
+  if (flags & ~(0xff | GEMM_EX_FIXED_ROWS)) return set_error(CAREL_ERR_ARG, "carel_gemm_split_plan: flags are a chain count | CAREL_PLAN_FIXED_ROWS");
+  tl_split_plan = 1; tl_plan_family = 0; tl_plan_npn = 0;
+  const int rc = carel::gemm_bf16_ex(a, (flags ? flags : 1) | GEMM_EX_PLAN_ONLY, nullptr);
+  if (rc) return rc;
+  plan[0] = tl_split_plan; plan[1] = tl_plan_family; plan[2] = tl_plan_npn;
+  return CAREL_OK;
+}
+#endif
+
 int carel::gemm_bf16_ex(const carel_gemm_args* a, int split_tile_factor, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!a) return set_error(CAREL_ERR_ARG, "carel_gemm_bf16: null args");
@@ -907,6 +944,10 @@ int carel::gemm_bf16_ex(const carel_gemm_args* a, int split_tile_factor, void* s
         const int npn = gemm_pp_pick_tn(q, splits);
         const long wgs = npn ? (long)(q.M / 256) * (q.N / (96 * npn)) * splits : 0;
         // (the same floor as gemm_pp_wgrad_splits: whatever carel_gemm_wgrad_splits proposes for this kernel must be taken by it)
+        if ((split_tile_factor & GEMM_EX_PLAN_ONLY) && npn && (g_gemm_variant == 3 || wgs >= 64)) {
+          tl_split_plan = 1; tl_plan_family = PLAN_PP; tl_plan_npn = npn;
+          return CAREL_OK;
+        }
 #ifdef CAREL_GEMM_ABLATE
         if (npn == 2 && g_gemm_variant >= 61 && g_gemm_variant <= 68) return gemm_pp_launch_tn_dbg(q, npn, splits, g_gemm_variant - 60, stream);
 #endif

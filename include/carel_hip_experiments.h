@@ -54,4 +54,17 @@ int carel_gemm_rowln(const carel_gemm_rowln_args* args, void* stream);
  * wave of carel_gemm_rowln loads per instruction is then one contiguous KiB.  Run it whenever the weight changes (after an optimiser step). */
 int carel_gemm_rowln_pack(const void* W, int64_t ldb, int32_t K, void* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Dispatch plans, for the tests that sweep the packed step over its row-count-dependent decisions (tests/test_packed_dispatch.py).
+ * carel_gemm_split_plan: what carel_gemm_bf16 would run for *args, without launching anything (the operands are not read; pointers
+ * must be non-null and aligned as for a launch).  flags: the number of equal GEMMs the caller runs side by side (the forward pass's
+ * chains, 1 or 2) | CAREL_PLAN_FIXED_ROWS when M does not depend on the batch (the [CLS]-only last layer).  plan[3] = { fp32 slabs of
+ * the internal split-K path (1 = single pass), kernel family CAREL_PLAN_*, tile width in units of 96 columns (ping-pong kernel; else 0) }.
+ * carel_encoder_workspace_bytes: the bytes the encoder gives that path (which = 0) and the weight-gradient slab area (which = 1).
+ * ---------------------------------------------------------------------------------------------- */
+#define CAREL_PLAN_FIXED_ROWS 0x100
+enum { CAREL_PLAN_PP = 1, CAREL_PLAN_128 = 2, CAREL_PLAN_BIG = 3, CAREL_PLAN_PP_SLABS = 4, CAREL_PLAN_128_SLABS = 5, CAREL_PLAN_SM = 6 };
+int carel_gemm_split_plan(const carel_gemm_args* args, int32_t flags, int32_t* plan);
+int64_t carel_encoder_workspace_bytes(int32_t batch, int32_t seq_len, int32_t which);
+
 #endif

@@ -51,7 +51,8 @@ def test_product_library_has_no_tuning_hooks_and_the_experiments_build_has_them(
         assert not hasattr(prod, n), "the product library exports the experiments-only symbol " + n
     import subprocess
     syms = subprocess.run(["nm", "-D", "--defined-only", lib_path], capture_output=True, text=True).stdout
-    for frag in ("gemm_tri", "gemm_rowln", "set_variant", "pair_enable", "gemm_pp_launch_pair"):
+    for frag in ("gemm_tri", "gemm_rowln", "set_variant", "pair_enable", "gemm_pp_launch_pair", "carel_gemm_split_plan",
+                 "carel_encoder_workspace_bytes"):
         assert frag not in syms, frag
     exp = ctypes.CDLL(build.lib_path(build.EXP_TAG))
     for n in header_functions() + exp_names:
