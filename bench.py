@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """CAREL-VAE training-step benchmark on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A "step" is one pass of the hot path (drl_classifier_ec_mmd_final_mul.py:823-845) over one resident batch:
@@ -9,6 +9,11 @@ forward (BERT-base encoder -> VAE tail -> loss) + backward + Adam (+ RCCL gradie
 Workload = BASELINE.json configs[1]: zh ECPE-shaped batch, 64 clause pairs per GPU, S = 128, vocabulary
 21 128, bag-of-words width 23 771, bf16 MFMA / fp32 accumulate, dropout active (model.train()).
 Prints ONE JSON line (rank 0).
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: nothing else.  --full adds every
+other figure after the timed steps: resident inputs, the per-GEMM roofline replay, the ECPE-shaped, inference, input-pipeline,
+English, sentence-transformer and ablation legs, and the CPU baseline with its ELBO parity.  Without it their keys are null
+(cpu_baseline, elbo_parity and speedup_vs_cpu_baseline are absent, as with --no-cpu-baseline).
 """
 import argparse
 import ctypes as C
@@ -51,8 +56,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=64, help="clause pairs per GPU")
     ap.add_argument("--shape", default="A", choices=["A", "B"], help="A dense (roofline headline), B ECPE-shaped lengths")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-ecpe", action="store_true", help="skip the secondary ECPE-shaped leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg (resident inputs, GEMM roofline, ECPE-shaped, inference, input "
+                         "pipeline, English, sentence-transformer, ablation heads, CPU baseline); off: the headline figure only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-ecpe", action="store_true", help="--full: skip the ECPE-shaped leg and the legs after it")
     ap.add_argument("--no-varlen", action="store_true", help="run padded positions through the encoder like the reference does")
     ap.add_argument("--torch-adam", action="store_true", help="use torch.optim.Adam instead of the fused HIP Adam")
     ap.add_argument("--adam-in-backward", action="store_true",
@@ -566,27 +574,30 @@ def main():
     log("timed region done: %.3f ms/step" % (1e3 * dt / a.steps))
     if a.dump_outputs and rank == 0:        # before the legs below run more steps on the same model
         dump_outputs(a.dump_outputs, model, loss)
-    # ---- the same step on resident inputs (batches already in HBM, no read-back): what the H2D + read-back cost on this box ----
-    for i in range(3):
-        step(i)
-    sync()
-    marks_r = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]
-    t_r = time.perf_counter()
-    marks_r[0].record()
-    for i in range(a.steps):
-        step(3 + i)
-        marks_r[i + 1].record()
-    sync()
-    dtr = time.perf_counter() - t_r
-    if world > 1:
-        t = torch.tensor([dtr], device=dev, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dtr = float(t.item())
-    resident = {"value": world * a.batch * a.steps / dtr, "unit": "clause-pairs/s", "ms_per_step": 1e3 * dtr / a.steps, "steps": a.steps,
-                "headline_over_resident": dt / dtr, "ms_per_step_in_order": [round(marks_r[i].elapsed_time(marks_r[i + 1]), 3) for i in range(a.steps)],
-                "note": "same step on batches that already sit in HBM, no loss read-back (rounds 1-3 quoted this as `value`); "
-                        "headline_over_resident = what the H2D copy + read-back cost on this box"}
-    log("resident inputs: %.3f ms/step (headline / resident = %.3f)" % (1e3 * dtr / a.steps, dt / dtr))
+    # ---- everything below, up to the result line, runs with --full only: a plain run is set-up, warm-up, timed steps ----
+    resident = None
+    if a.full:
+        # ---- the same step on resident inputs (batches already in HBM, no read-back): what the H2D + read-back cost on this box ----
+        for i in range(3):
+            step(i)
+        sync()
+        marks_r = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]
+        t_r = time.perf_counter()
+        marks_r[0].record()
+        for i in range(a.steps):
+            step(3 + i)
+            marks_r[i + 1].record()
+        sync()
+        dtr = time.perf_counter() - t_r
+        if world > 1:
+            t = torch.tensor([dtr], device=dev, dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dtr = float(t.item())
+        resident = {"value": world * a.batch * a.steps / dtr, "unit": "clause-pairs/s", "ms_per_step": 1e3 * dtr / a.steps, "steps": a.steps,
+                    "headline_over_resident": dt / dtr, "ms_per_step_in_order": [round(marks_r[i].elapsed_time(marks_r[i + 1]), 3) for i in range(a.steps)],
+                    "note": "same step on batches that already sit in HBM, no loss read-back (rounds 1-3 quoted this as `value`); "
+                            "headline_over_resident = what the H2D copy + read-back cost on this box"}
+        log("resident inputs: %.3f ms/step (headline / resident = %.3f)" % (1e3 * dtr / a.steps, dt / dtr))
     # roofline leg: the SAME step, 3 more times, with HIP events bracketing every GEMM launch on its stream.  It is kept
     # out of the timed region because the event markers between kernels cost ~5 % of step time (no kernel overlap at the
     # boundaries), and it runs the kernels SERIALLY (weight gradients back on the main stream): with two streams the
@@ -621,12 +632,14 @@ def main():
                 "avg_launch_us": us_hi, "avg_launch_us_kernel_only": us_lo, "frac_kernel_only": fl / n / (us_lo * 1e-6) / 1e12 / PEAK_BF16_TFLOPS,
                 "launches_per_step": n / nprof, "alg_gflop_per_launch": fl / n / 1e9, "gemm_ms_per_step": us_hi * n / nprof * 1e-3,
                 "event_calibration_us": {"empty_kernel_bracket": ov_e, "event_pair": ov_p}}
-    ev_timed, ov_empty_v, ov_pair_v = gemm_event_replay(a.warmup + a.steps)
+    ev_timed = None
+    if a.full:
+        ev_timed, ov_empty_v, ov_pair_v = gemm_event_replay(a.warmup + a.steps)
     pairs_per_s = world * a.batch * a.steps / dt
 
     # ---- secondary line: the same step on ECPE-shaped batches (SURVEY 8(d) shape-B: ~77 % padding), padding skipped ----
     ecpe = None
-    if a.shape == "A" and not a.no_varlen and not a.no_ecpe:
+    if a.full and a.shape == "A" and not a.no_varlen and not a.no_ecpe:
         bb, ll = [], []
         for i in range(4):
             b = synthetic_ecpe_batch(a.batch, 128, cfg.vocab_size, opt.pair_bow_dim, seed=101 + 10 * rank + i, shape="B")
@@ -665,7 +678,7 @@ def main():
 
     # ---- evaluation twin: get_pair_preds on a test-set-sized batch of ECPE-shaped pairs (:265-282, :958) ----
     infer = None
-    if not a.no_ecpe and rank == 0:
+    if a.full and not a.no_ecpe and rank == 0:
         tb = synthetic_ecpe_batch(2048, 128, cfg.vocab_size, opt.pair_bow_dim, seed=777, shape="B")
         ti, ta_, tt_ = (tb[k].to(dev) for k in ("input_ids", "attention_masks", "token_type_ids"))
         model.eval()
@@ -686,7 +699,7 @@ def main():
     # ---- config 4: the English three-space adversarial model (drl_classifier_en.py), one GPU ----
     english = None
     pipeline = sentence = ablation = None
-    if not a.no_ecpe and rank == 0 and world == 1:
+    if a.full and not a.no_ecpe and rank == 0 and world == 1:
         pipeline = input_pipeline_leg(dev, model, optim, a.batch)
         english = english_leg(dev, a.batch, max(5, a.steps // 2))
         sentence = sentence_transformer_leg(dev, max(5, a.steps // 2))
@@ -694,9 +707,7 @@ def main():
 
     # ---- roofline of the dominant kernel family ----
     roof = None
-    ms_t, fl_t, n_t = ev_timed
-
-    if n_t:
+    if ev_timed is not None and ev_timed[2]:          # (GEMM launches were recorded)
         traffic = None
         try:        # HBM traffic per GEMM launch from the committed PMC summary (rocprofv3 --pmc passes)
             for line in open(os.path.join(ROOT, "profiles", PMC_TRAFFIC_CSV)):
@@ -736,8 +747,8 @@ def main():
                       "wgrad_side_stream": bool(model.overlap_wgrad), "forward_chains": bool(model.overlap_wgrad and model.forward_chains),
                       "adam_in_backward": bool(getattr(optim, "_aux", None) is not None)},
            "roofline": roof, "resident_inputs": resident, "running_loss_lines": loss_lines[-2:], "ecpe_shaped": ecpe, "ablation_heads": ablation, "inference": infer, "english_adversarial": english, "input_pipeline": pipeline,
-           "sentence_transformer": sentence, "final_loss": final_loss}
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+           "sentence_transformer": sentence, "final_loss": final_loss, "full": a.full}
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         def hip_loss(P0, batch, eps_e, eps_c, ocfg2, oopt, fp32=False):
             m2 = M.DrlClassifier(M.make_opt(**vars(oopt)), M.encoder_config("zh", hidden_dropout=0.0, attn_dropout=0.0), seed=0)
             m2.load_state_dict(P0)

@@ -170,6 +170,17 @@ def test_bench_launches_its_own_ranks_and_checks_the_count(monkeypatch):
         bench.launch_ranks(a)
 
 
+def test_bench_other_legs_wait_for_full(monkeypatch):
+    """`bench.py --gpus 1 --steps N --warmup W` measures the headline alone; every other leg (roofline, resident inputs, ECPE-shaped,
+    inference, English, ablation, sentence-transformer, input pipeline, CPU baseline) runs only with --full."""
+    import importlib
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
+    assert bench.parse().full is True
+
+
 def test_mpnet_host_logic_bucket_map_and_state_dict_names():
     """CPU: the relative-position bucket map the model hands to the kernels is the oracle's (= transformers') function, entry by entry,
     and the MPNet sentence model speaks MPNetModel key names (round trip through load_state_dict / state_dict, no token types)."""
