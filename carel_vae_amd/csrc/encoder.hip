@@ -5,6 +5,8 @@
 // transformers BertModel.forward) and the encoder part of `loss.backward()` (:841).
 // Nothing is allocated here; every call only enqueues kernels on the caller's stream.
 #include <cstdlib>
+#include <mutex>
+#include <vector>
 #include "carel_hip_internal.h"
 
 using namespace carel;
@@ -377,6 +379,36 @@ static int forward_layers(const carel_encoder_args* a, int l0, int l1, long b0, 
   return CAREL_OK;
 }
 
+// Which batch's sorted embedding keys each scratch block holds: a host-side record, so that the backward pass needs no device read.
+// carel_encoder_forward sets the record of its scratch when it writes keys there and drops every record naming its act block (the
+// embedding statistics the keys go with are overwritten); carel_encoder_backward_embeddings takes the sorted path only on an exact match
+// -- same act block, same input_ids, same tok_row, same row count -- and the atomic path otherwise (a forward with scratch = NULL or in
+// inference mode, another batch's keys in this scratch).  `side`: the sort ran on the weight-gradient side stream.
+struct EmbedKeyRecord { const void* scratch; const void* act; const void* ids; const void* tok_row; long rows; bool side; };
+static std::mutex g_key_mu;
+static std::vector<EmbedKeyRecord> g_key_records;
+
+static long embed_rows_of(const carel_embed_args& e) { return (e.tok_row && e.n_rows > 0) ? (long)e.n_rows : (long)e.batch * e.seq_len; }
+
+static void embed_keys_written(const carel_encoder_args* a, const carel_embed_args* e, bool keys, bool side) {
+  std::lock_guard<std::mutex> lk(g_key_mu);
+  std::vector<EmbedKeyRecord>& r = g_key_records;
+  for (size_t i = 0; i < r.size();)
+    if (r[i].act == a->act || (keys && r[i].scratch == a->scratch)) { r[i] = r.back(); r.pop_back(); } else ++i;
+  if (keys) r.push_back(EmbedKeyRecord{a->scratch, a->act, a->input_ids, a->tok_row, embed_rows_of(*e), side});
+}
+
+// 1 = this scratch holds the sorted keys of exactly this batch (*side: sorted on the side stream), 0 = it does not
+static int embed_keys_match(const carel_encoder_args* a, const carel_embed_args* e, bool* side) {
+  std::lock_guard<std::mutex> lk(g_key_mu);
+  for (const EmbedKeyRecord& k : g_key_records)
+    if (k.scratch == a->scratch) {
+      *side = k.side;
+      return k.act == a->act && k.ids == a->input_ids && k.tok_row == a->tok_row && k.rows == embed_rows_of(*e);
+    }
+  return 0;
+}
+
 extern "C" int carel_encoder_forward(const carel_encoder_args* a, void* stream) {
   int rc = enc_check(a, "carel_encoder_forward");
   if (rc) return rc;
@@ -402,7 +434,11 @@ extern "C" int carel_encoder_forward(const carel_encoder_args* a, void* stream) 
         return set_error(CAREL_ERR_HIP, "carel_encoder_forward: event fork failed");
       if ((rc = embed_sort_rows(&e, sort_ws, ss->stream))) return rc;
     } else if ((rc = embed_sort_rows(&e, sort_ws, (hipStream_t)stream))) return rc;
-  } else if ((rc = carel_embed_ln_fwd(&e, stream))) return rc;
+    embed_keys_written(a, &e, true, ss != nullptr);
+  } else {
+    embed_keys_written(a, &e, false, false);
+    if ((rc = carel_embed_ln_fwd(&e, stream))) return rc;
+  }
   // Samples are independent through the whole encoder: with a->overlap_wgrad (dense rows, even batch) the two halves of
   // the batch run as two chains, one on `stream`, one on a peer stream of the same priority, so that each chain's launch gaps, tile-count
   // tails and memory-bound kernels are filled by the other's GEMMs.  The (optionally [CLS]-only) last layer runs whole.
@@ -616,8 +652,9 @@ extern "C" int carel_encoder_backward_join(const carel_encoder_args* a, void* st
   return CAREL_OK;
 }
 
-// Backward of the embedding block: a->dx = d(loss)/d(embedding output).  d_word_emb / d_pos_emb are
-// zeroed here and then accumulated with float atomics.
+// Backward of the embedding block: a->dx = d(loss)/d(embedding output).  d_word_emb / d_pos_emb are zeroed here and then written
+// by fixed-order segment sums over the keys carel_encoder_forward sorted for this batch, or accumulated with float atomics where
+// this scratch holds no such keys (embed_keys_match).
 extern "C" int carel_encoder_backward_embeddings(const carel_encoder_args* a, void* stream) {
   int rc = enc_check(a, "carel_encoder_backward_embeddings");
   if (rc) return rc;
@@ -633,9 +670,19 @@ extern "C" int carel_encoder_backward_embeddings(const carel_encoder_args* a, vo
   if (he == hipSuccess) he = hipMemsetAsync(a->d_pos_emb, 0, (size_t)a->max_pos * EH * 4, (hipStream_t)stream);
   if (he != hipSuccess) return set_error(CAREL_ERR_HIP, "carel_encoder_backward_embeddings: memset: %s", hipGetErrorString(he));
   // s.dy (f32 [T, 768]) is free here: scratch for the fixed-order position-table reduction
-  // (the sorted keys were made by carel_encoder_forward for this batch: same condition here as there)
+  // (sorted keys only where carel_encoder_forward left them in this scratch for this very batch; float atomics otherwise)
   const ScratchLayout sl = scratch_layout(B, S);
-  const void* sort_ws = embed_sort_supported(&e) ? (const char*)a->scratch + sl.o_sort : nullptr;
+  bool side = false;
+  const bool keyed = embed_sort_supported(&e) && embed_keys_match(a, &e, &side);
+  if (keyed && side && !(a->overlap_wgrad & 1)) {
+    // the keys were sorted on the side stream, and carel_encoder_backward_join above did not wait for it (overlap_wgrad off here)
+    SideStream* sd = side_stream();
+    if (!sd) return set_error(CAREL_ERR_HIP, "carel_encoder_backward_embeddings: no side stream");
+    hipEvent_t ev = sd->ev[SideStream::NEV - 1];
+    if (hipEventRecord(ev, sd->stream) != hipSuccess || hipStreamWaitEvent((hipStream_t)stream, ev, 0) != hipSuccess)
+      return set_error(CAREL_ERR_HIP, "carel_encoder_backward_embeddings: event join failed");
+  }
+  const void* sort_ws = keyed ? (const char*)a->scratch + sl.o_sort : nullptr;
   return embed_ln_bwd_ex(&e, a->dx, a->d_word_emb, a->d_pos_emb, a->d_type_emb, a->d_emb_ln_g, a->d_emb_ln_b, s.part, s.dy, (hipStream_t)stream, sort_ws);
 }
 

@@ -574,10 +574,11 @@ extern "C" int carel_embed_ln_fwd(const carel_embed_args* a, void* stream_) {
 }
 
 namespace carel {
-// can the table gradients of this batch come from sorted keys (embed_sort_kernel's limits)?
+// can the table gradients of this batch come from sorted keys (embed_sort_kernel's limits)?  Ids stay below 2^19 - 1: the key of id
+// 2^19 - 1 at row 8191 would be 0xFFFFFFFF, the filler / padding sentinel, and that row's gradient would be dropped
 int embed_sort_supported(const carel_embed_args* a) {
   const long rows = (a->tok_row && a->n_rows > 0) ? (long)a->n_rows : (long)a->batch * a->seq_len;
-  return rows >= 1 && rows <= EMB_SORT_MAX && a->vocab_size <= (1 << (32 - EMB_ROW_BITS)) && a->max_pos <= (1 << (32 - EMB_ROW_BITS));
+  return rows >= 1 && rows <= EMB_SORT_MAX && a->vocab_size < (1 << (32 - EMB_ROW_BITS)) && a->max_pos < (1 << (32 - EMB_ROW_BITS));
 }
 size_t embed_sort_bytes() { return (size_t)EMB_SORT_MAX * 8 + 2 * (size_t)EMB_SORT_MAX * 4; }      // row keys int2 [8192] | sorted keys u32 [2][8192]
 // carel_embed_ln_fwd that also leaves the (token id, position id) of every row in `sort_ws`; embed_sort_rows then sorts them (any stream

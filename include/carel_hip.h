@@ -279,7 +279,13 @@ int carel_relpos_reduce(const void* ddist_f32_BHx256, int32_t batch, const void*
  *             needs (inference = 1: one layer's worth, re-used by every layer; no backward possible)
  *   scratch : carel_encoder_scratch_bytes(B, S) bytes of workspace.  ZERO-FILL IT ONCE when it is allocated, and let nothing but the library
  *             write to it afterwards (ABI 5): a few words of it are flags of the pair split-K GEMMs (carel_gemm_args.splitk_ws_zeroed), which
- *             must not start out equal to a launch sequence number
+ *             must not start out equal to a launch sequence number.  A training forward (inference = 0, scratch != NULL,
+ *             B*S or n_tokens <= 8192 rows, vocab_size and max_pos < 2^19) also leaves the batch's sorted embedding keys in it;
+ *             carel_encoder_backward_embeddings then writes the word / position table gradients as fixed-order sums
+ *             (bit-reproducible) if the last forward that wrote keys into this scratch had the same act, input_ids, tok_row and
+ *             row count and no later forward ran on that act.  Otherwise (a forward with scratch = NULL or with other ids, any
+ *             forward in between on the same act) it falls back to float atomics: correct, not bit-reproducible.  The record is kept
+ *             on the host by pointer: rewriting input_ids in place between forward and backward breaks the pairing unnoticed
  *   dx      : f32 [B*S, 768]; in: d(loss)/d(last hidden state); carried down through the layers
  * Constraints: hidden 768, 12 heads, intermediate 3072, seq_len in {32,64,96,128}, B*S % 128 == 0.
  * ---------------------------------------------------------------------------------------------- */

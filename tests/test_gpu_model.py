@@ -2,6 +2,7 @@
   (a) the golden vectors produced by the reference's own classes (fp32 CPU)      -> bf16-level tolerance
   (b) the CPU oracle run with bf16 rounding at the kernels' storage points       -> tight tolerance
 for forward terms, latent means, gradients and a 3-step Adam trajectory."""
+import dataclasses
 import os
 
 import numpy as np
@@ -614,22 +615,31 @@ def test_bench_shape_backward_and_adam_vs_oracle(shape):
             assert float((d <= 0.2 * opt.vae_lr).float().mean()) >= 0.90, (k, float((d <= 0.2 * opt.vae_lr).float().mean()))
 
 
-@pytest.mark.parametrize("shape,variant", [("A", "zh"), ("B", "zh"), ("B", "roberta")])
+@pytest.mark.parametrize("shape,variant", [("A", "zh"), ("B", "zh"), ("B", "roberta"), ("corpus", "zh"), ("corpus", "roberta")])
 def test_embedding_table_gradients_are_bit_reproducible(shape, variant):
     """Round 4: the word / position table gradients come from fixed-order segment sums over keys sorted in the forward pass
     (csrc/ln.hip: embed_sort_kernel, embed_segsum_kernel) instead of 6.3 M float atomics -- the library's last order-dependent sum.
-    A small vocabulary (every id ~8 times per batch, [CLS]-like ids 64 times), dense and packed rows, BERT and RoBERTa position ids:
-    three passes over the same batch give bit-identical gradients for EVERY parameter, with the side stream on and off; and the
-    table gradients equal an fp64 index_add of the same rows to fp32 rounding (a wrong run boundary would drop or double a row)."""
+    A small vocabulary (every id ~8 times per batch, [CLS]-like ids 64 times) or batches of the ECPE corpus (tests/ecpe_batches.py:
+    [CLS] / <s> runs of 64, [SEP] / </s> runs of 128), dense and packed rows, BERT and RoBERTa position ids: three passes over the same
+    batch give bit-identical gradients for EVERY parameter, with the side stream on and off, and the table gradients are nonzero on
+    exactly the rows the batch uses.  The 4e-2 norm bound below is a coarse check against the fp32 oracle only: the row-by-row
+    parity of the table gradients with a float64 index_add, at the run lengths where a dropped or doubled row would show, is asserted in
+    tests/test_gpu_embed_grad.py."""
     if variant == "roberta":
         cfg = O.EncoderConfig(layers=2, vocab_size=1000, max_pos=514, type_vocab=1, ln_eps=1e-5, variant="roberta", pad_id=1)
         opt = O.Opt(language="en", pair_bow_dim=257, dropout=0.0)
     else:
         cfg, opt = O.EncoderConfig(layers=2, vocab_size=1000), O.Opt(pair_bow_dim=257, dropout=0.0)
+    if shape == "corpus":
+        cfg = dataclasses.replace(cfg, vocab_size=21128)                # the corpus's character ids reach ~3 000
     model, P = build(cfg, opt, 7)
     model.train()
-    batch = O.synthetic_batch(64, 128, cfg, opt.pair_bow_dim, seed=5, shape=shape)
-    batch["input_ids"][:, 0] = 2                                      # one id in every sample: a 64-row run
+    if shape == "corpus":
+        from tests.ecpe_batches import corpus_batch
+        batch, _ = corpus_batch(64, 128, cfg, opt, seed=5)
+    else:
+        batch = O.synthetic_batch(64, 128, cfg, opt.pair_bow_dim, seed=5, shape=shape)
+        batch["input_ids"][:, 0] = 2                                  # one id in every sample: a 64-row run
     g = torch.Generator().manual_seed(3)
     eps_e, eps_c = torch.randn(opt.ec_dim, generator=g), torch.randn(opt.ec_dim, generator=g)
     runs = []
