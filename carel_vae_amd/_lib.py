@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CAREL_HIP_LIB") or os.path.join(_HERE, "libcarel_hip.so")     # CAREL_HIP_LIB: an experiment build (tools/ablate_*.sh, tools/ab_lib.sh)
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 
 class CarelError(RuntimeError):
@@ -68,7 +68,7 @@ class AttnArgs(C.Structure):
                 ("batch", C.c_int32), ("seq_len", C.c_int32), ("heads", C.c_int32), ("head_dim", C.c_int32),
                 ("drop_seed", C.c_uint32), ("drop_site", C.c_uint32), ("drop_idx_offset", C.c_uint32),
                 ("drop_p", C.c_float), ("cu_seqlens", C.c_void_p), ("rel_bias_dist", C.c_void_p), ("d_rel_bias_dist", C.c_void_p),
-                ("q_rows", C.c_int32)]
+                ("q_rows", C.c_int32), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
 class TailArgs(C.Structure):
@@ -289,6 +289,9 @@ SIGNATURES = {
     "carel_attention_bwd": (C.c_int, [C.POINTER(AttnArgs), C.c_void_p]),
     "carel_relpos_expand": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "carel_relpos_reduce": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "carel_attention_bwd_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "carel_relpos_expand_span": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "carel_relpos_reduce_span": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
 }
 
 # entry points of the EXPERIMENTS build only (include/carel_hip_experiments.h): tuning hooks + the kernels that were not adopted

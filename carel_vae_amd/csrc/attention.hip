@@ -462,7 +462,7 @@ using namespace carel;
 static int attn_prepare(const carel_attn_args* a, AttnParams* p, const char* who, bool bwd) {
   if (!a) return set_error(CAREL_ERR_ARG, "%s: null args", who);
   if (a->heads != NH || a->head_dim != HD) return set_error(CAREL_ERR_SHAPE, "%s: heads/head_dim must be %d/%d", who, NH, HD);
-  if (a->seq_len < 32 || a->seq_len > 128 || (a->seq_len & 31)) return set_error(CAREL_ERR_SHAPE, "%s: seq_len must be 32, 64, 96 or 128 (got %d)", who, a->seq_len);
+  if (a->seq_len < 32 || a->seq_len > 512 || (a->seq_len & 31)) return set_error(CAREL_ERR_SHAPE, "%s: seq_len must be a multiple of 32 in [32, 512] (got %d)", who, a->seq_len);
   if (a->batch <= 0) return set_error(CAREL_ERR_SHAPE, "%s: batch must be positive", who);
   if (!a->qkv || !a->ctx || !a->lse) return set_error(CAREL_ERR_ARG, "%s: null tensor", who);
   if (bwd && (!a->dctx || !a->dqkv)) return set_error(CAREL_ERR_ARG, "%s: null gradient tensor", who);
@@ -482,6 +482,7 @@ extern "C" int carel_attention_fwd(const carel_attn_args* a, void* stream_) {
   AttnParams p;
   int rc = attn_prepare(a, &p, "carel_attention_fwd", false);
   if (rc) return rc;
+  if (p.S > 128) return attn_long_fwd(a, stream);       // flash-style kernels (attention_long.hip)
   const bool drop = p.drop.thresh != 0;
   if (p.rel) {
     if (drop) hipLaunchKernelGGL((attn_fwd_kernel<true, true>), dim3(p.B * NH), dim3(256), 0, stream, p);
@@ -498,6 +499,7 @@ extern "C" int carel_attention_bwd(const carel_attn_args* a, void* stream_) {
   AttnParams p;
   int rc = attn_prepare(a, &p, "carel_attention_bwd", true);
   if (rc) return rc;
+  if (p.S > 128) return attn_long_bwd(a, stream);
   static bool attr_set = false;     // idempotent; a benign race sets it twice
   if (!attr_set) {
     hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_BWD_LDS);

@@ -65,7 +65,7 @@ struct Scratch { char* dy; char* dyb; char* dyb2; char* du; char* dctx; char* dq
 // The operands of a layer's weight gradients -- dyb, dyb2, du, dqkv and the two LayerNorm-backward partial buffers -- exist TWICE, used by
 // layers of even / odd index: the layer's weight gradients run as one grouped launch on the side stream after its attention backward
 // and may still be reading them while the main stream is already writing the next layer's (round 4; 113 MB at T = 8192).
-struct ScratchLayout { size_t o_dy, o_dyb[2], o_dyb2[2], o_du[2], o_dctx, o_dqkv[2], o_slabs, o_ws, o_part[2], o_part2, o_part3[2], o_sort, ws_bytes, slab_bytes, total; };
+struct ScratchLayout { size_t o_dy, o_dyb[2], o_dyb2[2], o_du[2], o_dctx, o_dqkv[2], o_slabs, o_ws, o_part[2], o_part2, o_part3[2], o_sort, o_attn, attn_bytes, ws_bytes, slab_bytes, total; };
 
 // split-K factor of the weight-gradient GEMMs (K = tokens): chosen by the GEMM library for the kernel it will run
 int wgrad_splits(long T, int M, int N) { return carel_gemm_wgrad_splits(M, N, T); }
@@ -104,6 +104,9 @@ ScratchLayout scratch_layout(long B, long S) {
   }
   s.o_part2 = o; o += al(part);             // DGELU column-sum partials
   s.o_sort = o; o += al(embed_sort_bytes());  // (token id, position id) of every row + their sorted keys: the embedding tables' gradients without atomics
+  // S > 128: the long-sequence attention backward's workspace (delta and, with the MPNet bias, its gradient partials); 0 bytes at S <= 128
+  s.attn_bytes = (size_t)carel_attention_bwd_workspace_bytes((int32_t)B, (int32_t)S, 1);
+  s.o_attn = o; o += al(s.attn_bytes);
   s.total = o;
   return s;
 }
@@ -123,7 +126,7 @@ int enc_check(const carel_encoder_args* a, const char* who) {
   if (a->hidden != EH || a->heads != ENH || a->intermediate != EI)
     return set_error(CAREL_ERR_SHAPE, "%s: only the BERT-base geometry (768/12/3072) is supported", who);
   if (a->batch < 1 || a->n_layers < 1) return set_error(CAREL_ERR_SHAPE, "%s: bad batch / n_layers", who);
-  if (a->seq_len < 32 || a->seq_len > 128 || (a->seq_len & 31)) return set_error(CAREL_ERR_SHAPE, "%s: seq_len must be 32/64/96/128", who);
+  if (a->seq_len < 32 || a->seq_len > 512 || (a->seq_len & 31)) return set_error(CAREL_ERR_SHAPE, "%s: seq_len must be a multiple of 32 in [32, 512]", who);
   if (((long)a->batch * a->seq_len) % 128) return set_error(CAREL_ERR_SHAPE, "%s: batch*seq_len must be a multiple of 128 (pad the batch)", who);
   if (!a->input_ids || !a->layers || !a->act) return set_error(CAREL_ERR_ARG, "%s: null tensor", who);
   if (a->n_cls) {
@@ -292,6 +295,7 @@ static int forward_layers(const carel_encoder_args* a, int l0, int l1, long b0, 
     const bool cls_only = a->n_cls > 0 && i + 1 == a->n_layers;
     // the [CLS]-only last layer reads one context row per sample (position 0): the other query tiles are never computed
     at.q_rows = cls_only ? 32 : 0;
+    at.workspace = nullptr; at.workspace_bytes = 0;
     if ((rc = carel_attention_fwd(&at, stream))) return rc;
     if (cls_only && !whole) return set_error(CAREL_ERR_ARG, "carel_encoder_forward: internal: [CLS]-only layer on a partial batch");
     long R = T;                                  // rows of the row-wise half of this layer
@@ -612,6 +616,7 @@ extern "C" int carel_encoder_backward_layer(const carel_encoder_args* a, int32_t
   at.cu_seqlens = a->cu_seqlens;
   at.rel_bias_dist = a->rel_bias_dist; at.d_rel_bias_dist = a->d_rel_bias_dist;
   at.q_rows = cls_only ? 32 : 0;                 // dctx is zero off the [CLS] rows: only the first query tile carries a gradient
+  at.workspace = (char*)a->scratch + sl.o_attn; at.workspace_bytes = (int64_t)sl.attn_bytes;
   if (a->tok_row && layer + 2 >= a->n_layers) {
     // packed: the attention backward writes only rows that belong to a sample; the filler rows up to the next multiple
     // of 128 must be exact zeros for the column sums / dgrad / wgrad GEMMs that read dqkv over all T rows.  Once per backward pass and

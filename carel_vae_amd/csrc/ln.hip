@@ -557,8 +557,13 @@ static int embed_check(const carel_embed_args* a, const char* who) {
   if (a->hidden != H) return set_error(CAREL_ERR_SHAPE, "%s: hidden must be %d (got %d)", who, H, a->hidden);
   if (!a->input_ids || !a->word_emb || !a->pos_emb || !a->type_emb || !a->ln_gamma || !a->ln_beta)
     return set_error(CAREL_ERR_ARG, "%s: null tensor", who);
-  if (a->batch <= 0 || a->seq_len <= 0 || a->type_vocab < 1 || a->type_vocab > 2 || a->seq_len > a->max_pos)
+  if (a->batch <= 0 || a->seq_len <= 0 || a->type_vocab < 1 || a->type_vocab > 2)
     return set_error(CAREL_ERR_SHAPE, "%s: bad batch/seq_len/type_vocab", who);
+  // position ids run 0 .. S-1 (BERT) or pad_id + 1 .. pad_id + S (RoBERTa / MPNet): all of them must be rows of the position table
+  const long pos_limit = a->roberta ? (long)a->max_pos - a->pad_id - 1 : (long)a->max_pos;
+  if (a->seq_len > pos_limit)
+    return set_error(CAREL_ERR_SHAPE, "%s: seq_len %d runs past the position table (max_pos %d%s: at most %ld positions)", who, a->seq_len,
+                     a->max_pos, a->roberta ? ", ids from pad_id + 1" : "", pos_limit);
   return CAREL_OK;
 }
 

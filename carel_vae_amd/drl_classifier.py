@@ -365,6 +365,23 @@ class _Call:
     pass
 
 
+
+def rel_span(S):
+    """Entries of the MPNet bias-by-distance row the attention kernels read at length S: 256 (S <= 128), 1024 (S > 128)."""
+    return 256 if S <= 128 else 1024
+
+
+def mpnet_bucket_by_distance(span):
+    """int32 [span]: entry i = transformers MPNetEncoder.relative_position_bucket of the distance key - query = i - (span/2 - 1)
+    (num_buckets 32, max_distance 128; the same float32 log and truncation); the last entry is unused."""
+    rel = torch.arange(-(span // 2 - 1), span // 2 + 1, dtype=torch.long)
+    n = -rel
+    ret = (n < 0).to(torch.long) * 16
+    n = torch.abs(n)
+    large = 8 + (torch.log(n.float() / 8) / math.log(128 / 8) * 8).to(torch.long)
+    ret = ret + torch.where(n < 8, n, torch.min(large, torch.full_like(large, 15)))
+    return ret.to(torch.int32)
+
 class DrlClassifier(nn.Module):
     """Reference `DrlClassifier` (:149-534).  Same constructor argument, attribute names, `forward`,
     `get_pair_preds`, `get_params`, state_dict keys."""
@@ -687,44 +704,74 @@ class DrlClassifier(nn.Module):
         a.d_word_emb, a.d_pos_emb, a.d_type_emb = self._g(e + "word_embeddings.weight"), self._g(e + "position_embeddings.weight"), self._g(e + "token_type_embeddings.weight")
         a.d_emb_ln_g, a.d_emb_ln_b = self._g(e + "LayerNorm.weight"), self._g(e + "LayerNorm.bias")
         if getattr(c, "rel_pos", False):
-            r = self._rel_buffers(int(a.batch))
-            L.check(L.load().carel_relpos_expand(self._w(REL_KEY), r.bucket.data_ptr(), r.dist.data_ptr(), L.current_stream()), "carel_relpos_expand")
+            span = rel_span(S)
+            r = self._rel_buffers(int(a.batch), span)
+            lib = L.load()
+            if span == 256:
+                L.check(lib.carel_relpos_expand(self._w(REL_KEY), r.bucket.data_ptr(), r.dist.data_ptr(), L.current_stream()), "carel_relpos_expand")
+            else:
+                L.check(lib.carel_relpos_expand_span(self._w(REL_KEY), r.bucket.data_ptr(), r.dist.data_ptr(), span, L.current_stream()),
+                        "carel_relpos_expand_span")
             a.rel_bias_dist, a.d_rel_bias_dist = r.dist.data_ptr(), r.ddist.data_ptr()
         return a
 
-    def _rel_buffers(self, batch=1):
-        """MPNet relative positions: bucket[i] = relative_position_bucket(i - 127) with the expression of transformers
-        MPNetEncoder.relative_position_bucket (num_buckets 32, max_distance 128), the bias by distance [12, 256] made from the
+    def _rel_buffers(self, batch=1, span=256):
+        """MPNet relative positions: bucket[i] = relative_position_bucket(i - (span/2 - 1)) with the expression of transformers
+        MPNetEncoder.relative_position_bucket (num_buckets 32, max_distance 128), the bias by distance [12, span] made from the
         learned table before every forward, and the gradient by distance, one row per (sample, head), that the attention backward
-        kernels add into without atomics (bit-reproducible; carel_relpos_reduce sums the samples in order)."""
-        r = getattr(self, "_rel", None)
+        kernels add into without atomics (bit-reproducible; carel_relpos_reduce sums the samples in order).  span 256 for S <= 128,
+        1024 for the long-sequence kernels (rel_span)."""
+        cache = getattr(self, "_rel_by_span", None)
+        if cache is None:
+            cache = self._rel_by_span = {}
+        r = cache.get(span)
         dev = self._flat.device
         if r is None or r.bucket.device != dev:
-            rel = torch.arange(-127, 129, dtype=torch.long)
-            n = -rel
-            ret = (n < 0).to(torch.long) * 16
-            n = torch.abs(n)
-            large = 8 + (torch.log(n.float() / 8) / math.log(128 / 8) * 8).to(torch.long)
-            ret = ret + torch.where(n < 8, n, torch.min(large, torch.full_like(large, 15)))
-            r = self._rel = SimpleNamespace(bucket=ret.to(torch.int32).to(dev).contiguous(),
-                                            dist=torch.zeros((NH, 256), device=dev, dtype=torch.float32),
-                                            ddist=torch.zeros((NH, 256), device=dev, dtype=torch.float32))
+            r = cache[span] = SimpleNamespace(bucket=mpnet_bucket_by_distance(span).to(dev).contiguous(),
+                                              dist=torch.zeros((NH, span), device=dev, dtype=torch.float32),
+                                              ddist=torch.zeros((NH, span), device=dev, dtype=torch.float32))
         if r.ddist.shape[0] < batch * NH:
-            r.ddist = torch.zeros((batch * NH, 256), device=dev, dtype=torch.float32)
+            r.ddist = torch.zeros((batch * NH, span), device=dev, dtype=torch.float32)
         return r
 
     @staticmethod
-    def _prep_ids(t, Bp):
+    def _prep_ids(t, Bp, Sp=None, fill=0):
+        """[B, S] -> [Bp, Sp] int64: zero rows below (filler samples), `fill` columns on the right (positions that pad the length up
+        to a multiple of 32: token ids get pad_id, the attention mask 0)."""
         t = t.to(torch.long).contiguous()
+        if Sp is not None and t.shape[1] != Sp:
+            t = torch.cat((t, torch.full((t.shape[0], Sp - t.shape[1]), fill, dtype=t.dtype, device=t.device)), dim=1)
         if t.shape[0] != Bp:
             pad = torch.zeros((Bp - t.shape[0], t.shape[1]), dtype=t.dtype, device=t.device)
             t = torch.cat((t, pad), dim=0)
         return t
 
     @staticmethod
+    def _padded_len(S, max_pos=512, roberta=0, pad_id=0, adapter="false"):
+        """The length the encoder runs for inputs of S positions: S rounded up to a multiple of 32, at most 512 and at most the rows of
+        the position table (BERT: max_pos; RoBERTa / MPNet, whose ids start at pad_id + 1: max_pos - pad_id - 1).  The extra positions
+        are masked: a masked key contributes exactly zero and the packed path skips it, so every result equals a run at the rounded
+        length.  Sentence adapters attend to padding too: they keep S in {32, 64, 96, 128}."""
+        limit = min(512, max_pos - pad_id - 1 if roberta else max_pos)
+        if S < 1 or S > limit:
+            raise L.CarelError("sequence length must be at most %d (--max_len; the position table has %d rows%s); got %d"
+                               % (limit, max_pos, ", ids from pad_id + 1" if roberta else "", S))
+        Sp = (S + 31) // 32 * 32
+        if adapter not in ("false", False, None) and (Sp != S or S > 128):
+            raise L.CarelError("with a sentence adapter the sequence length must be 32, 64, 96 or 128 (--max_len; adapters attend to "
+                               "padded positions); got %d" % S)
+        return Sp
+
+    def _padded_shape(self, B, S):
+        """(Bp, Sp): the batch and length the encoder runs (_padded_len, _padded_batch) for this model."""
+        c = self.cfg
+        Sp = self._padded_len(S, c.max_pos, c.roberta, c.pad_id, getattr(self, "adapter", "false"))
+        return self._padded_batch(B, Sp), Sp
+
+    @staticmethod
     def _padded_batch(B, S):
-        if S < 32 or S > 128 or S % 32:
-            raise L.CarelError("sequence length must be 32, 64, 96 or 128 (--max_len); got %d" % S)
+        if S < 32 or S > 512 or S % 32:
+            raise L.CarelError("sequence length must be a multiple of 32 in [32, 512] (--max_len); got %d" % S)
         Bp = B
         while (Bp * S) % 128:
             Bp += 1
@@ -789,11 +836,11 @@ class DrlClassifier(nn.Module):
         self._require_cuda()
         ops._chk_cuda(input_ids, att_masks, token_type_ids, content_bow)
         B, S = input_ids.shape
-        Bp = self._padded_batch(B, S)
+        Bp, S = self._padded_shape(B, S)
         c = _Call()
         c.B, c.S, c.Bp = B, S, Bp
-        c.ids, c.att = self._prep_ids(input_ids, Bp), self._prep_ids(att_masks, Bp)
-        c.tt = None if token_type_ids is None else self._prep_ids(token_type_ids, Bp)
+        c.ids, c.att = self._prep_ids(input_ids, Bp, S, self.cfg.pad_id), self._prep_ids(att_masks, Bp, S)
+        c.tt = None if token_type_ids is None else self._prep_ids(token_type_ids, Bp, S)
         dev = input_ids.device
         f32 = torch.float32
         c.labels = dict(emo=emotion_labels.to(dev, torch.long).reshape(-1).contiguous(), cau=cause_labels.to(dev, f32).reshape(-1).contiguous(),
@@ -957,7 +1004,8 @@ class DrlClassifier(nn.Module):
             if self._adam_hook is not None and not accumulate and (self._dp is None or work is not None):
                 self._adam_hook._layer_ready(l, after=work)
 
-        rel = self._rel_buffers(int(ea.batch)) if getattr(self.cfg, "rel_pos", False) else None
+        span = rel_span(int(ea.seq_len))
+        rel = self._rel_buffers(int(ea.batch), span) if getattr(self.cfg, "rel_pos", False) else None
         if rel is not None:
             if rel.ddist.data_ptr() != ea.d_rel_bias_dist:
                 raise L.CarelError("internal: the relative-position gradient buffer was re-allocated between forward and backward")
@@ -972,7 +1020,11 @@ class DrlClassifier(nn.Module):
             layer_ready(0)
         L.check(lib.carel_encoder_backward_embeddings(C.byref(ea), st), "carel_encoder_backward_embeddings")
         if rel is not None:      # fold the gradient by distance (every layer's attention backward added to it) into the table's buckets
-            L.check(lib.carel_relpos_reduce(rel.ddist.data_ptr(), int(ea.batch), rel.bucket.data_ptr(), self._g(REL_KEY), 0, st), "carel_relpos_reduce")
+            if span == 256:
+                L.check(lib.carel_relpos_reduce(rel.ddist.data_ptr(), int(ea.batch), rel.bucket.data_ptr(), self._g(REL_KEY), 0, st), "carel_relpos_reduce")
+            else:
+                L.check(lib.carel_relpos_reduce_span(rel.ddist.data_ptr(), int(ea.batch), rel.bucket.data_ptr(), self._g(REL_KEY), 0, span, st),
+                        "carel_relpos_reduce_span")
 
     def _bind_grads(self):
         if self._grad_views is None:
@@ -1045,17 +1097,17 @@ class DrlClassifier(nn.Module):
         ops._chk_cuda(input_ids, att_masks, token_type_ids)
         dev = input_ids.device
         eps_e, eps_c = self._draw_noise(dev)
-        N, S = input_ids.shape
+        N, S0 = input_ids.shape
         out = torch.empty(N, device=dev, dtype=torch.float32)
         self._refresh_shadow()
         lib = L.load()
         for s in range(0, N, chunk):
             ids = input_ids[s:s + chunk]
             B = ids.shape[0]
-            Bp = self._padded_batch(B, S)
-            ids = self._prep_ids(ids, Bp)
-            att = self._prep_ids(att_masks[s:s + chunk], Bp)
-            tt = None if token_type_ids is None else self._prep_ids(token_type_ids[s:s + chunk], Bp)
+            Bp, S = self._padded_shape(B, S0)
+            ids = self._prep_ids(ids, Bp, S, self.cfg.pad_id)
+            att = self._prep_ids(att_masks[s:s + chunk], Bp, S)
+            tt = None if token_type_ids is None else self._prep_ids(token_type_ids[s:s + chunk], Bp, S)
             ws = self._workspace(Bp, S, inference=True)
             pack = self._pack_info(att, B, Bp, S)
             cls = self._cls_info(B, Bp, S, pack, dev)

@@ -247,11 +247,11 @@ class DrlClassifier(_Base):
         self._require_cuda()
         ops._chk_cuda(input_ids, att_masks, token_type_ids, content_bow)
         B, S = input_ids.shape
-        Bp = self._padded_batch(B, S)
+        Bp, S = self._padded_shape(B, S)
         c = _Call()
         c.B, c.S, c.Bp = B, S, Bp
-        c.ids, c.att = self._prep_ids(input_ids, Bp), self._prep_ids(att_masks, Bp)
-        c.tt = None if token_type_ids is None else self._prep_ids(token_type_ids, Bp)
+        c.ids, c.att = self._prep_ids(input_ids, Bp, S, self.cfg.pad_id), self._prep_ids(att_masks, Bp, S)
+        c.tt = None if token_type_ids is None else self._prep_ids(token_type_ids, Bp, S)
         dev, f32 = input_ids.device, torch.float32
         c.labels = dict(emo=emotion_labels.to(dev, f32).reshape(-1).contiguous(), cau=cause_labels.to(dev, f32).reshape(-1).contiguous(),
                         pair=pair_labels.to(dev, f32).reshape(-1).contiguous(), bow=content_bow.to(dev, f32).contiguous())
@@ -452,7 +452,7 @@ class DrlClassifier(_Base):
             self._noise = None
         else:
             eps_e, eps_c = torch.randn(o.ec_dim, device=dev), torch.randn(o.ec_dim, device=dev)     # emotion first (:347-348)
-        N, S = input_ids.shape
+        N, S0 = input_ids.shape
         out = torch.empty(N, device=dev, dtype=torch.float32)
         self._refresh_shadow()
         lib = L.load()
@@ -460,11 +460,11 @@ class DrlClassifier(_Base):
         for s in range(0, N, chunk):
             ids = input_ids[s:s + chunk]
             B = ids.shape[0]
-            Bp = self._padded_batch(B, S)
+            Bp, S = self._padded_shape(B, S0)
             c = _Call()
             c.B, c.S, c.Bp, c.labels, c.seed = B, S, Bp, None, 0
-            ids, att = self._prep_ids(ids, Bp), self._prep_ids(att_masks[s:s + chunk], Bp)
-            tt = None if token_type_ids is None else self._prep_ids(token_type_ids[s:s + chunk], Bp)
+            ids, att = self._prep_ids(ids, Bp, S, self.cfg.pad_id), self._prep_ids(att_masks[s:s + chunk], Bp, S)
+            tt = None if token_type_ids is None else self._prep_ids(token_type_ids[s:s + chunk], Bp, S)
             ws = self._workspace(Bp, S, inference=True)
             pack = self._pack_info(att, B, Bp, S)
             cls = self._cls_info(B, Bp, S, pack, dev)

@@ -25,9 +25,10 @@ Two known deviations from what the reference's scripts most likely ran (both PAR
     sentence-transformers of the reference's era (09/2021) defaulted to transformers.AdamW: eps 1e-6 and decay applied AFTER the update.
     `optimizer_params={"eps": 1e-6}` selects that epsilon; the decay order differs by a factor (1 - lr * wd) on the update of one step
     (2e-7 relative at the default lr 2e-5, wd 0.01).
-  * sequence length: max_seq_length defaults to 128 because the attention kernels hold one (sample, head) per workgroup with S <= 128;
-    all-mpnet-base-v2 ships max_seq_length 384.  ECPE clauses are far shorter (p99 70-89 tokens); a sentence that IS longer
-    is truncated by the tokenizer, and tokenize() warns once when that happens instead of truncating silently.
+  * sequence length: max_seq_length defaults to 128 (the package's default for all-mpnet-base-v2 is 384); any value up to 512 works
+    (lengths that are not a multiple of 32 run padded up to one, with masked positions: exact).  ECPE clauses are far shorter (p99 70-89
+    tokens); a sentence that IS longer than max_seq_length is truncated by the tokenizer, and tokenize() warns once when that
+    happens instead of truncating silently.
 """
 import ctypes as C
 import math
@@ -124,6 +125,7 @@ class SentenceTransformer(nn.Module):
         self._m = M.DrlClassifier(M.make_opt(pair_bow_dim=8), cfg, seed=seed)
         self._m.cls_only_last = False            # mean pooling reads every attended token of the last layer
         self.tokenizer, self.max_seq_length = tokenizer, int(max_seq_length)
+        M.DrlClassifier._padded_len(self.max_seq_length, cfg.max_pos, cfg.roberta, cfg.pad_id)     # CarelError past the position table / 512
         self._fwd = 0
         if self.mpnet:                                   # MPNetEmbeddings has no token types: the engine's row stays zero
             with torch.no_grad():
@@ -193,8 +195,8 @@ class SentenceTransformer(nn.Module):
                 for t in texts]
         if not getattr(self, "_warned_truncation", False) and any(int(r["attention_mask"].sum()) >= self.max_seq_length for r in rows):
             import warnings
-            warnings.warn("SentenceTransformer.tokenize: a sentence fills all %d positions and was probably truncated (the attention kernels "
-                          "cap the sequence at 128 tokens; all-mpnet-base-v2 itself allows 384)" % self.max_seq_length)
+            warnings.warn("SentenceTransformer.tokenize: a sentence fills all %d positions and was probably truncated (max_seq_length may be "
+                          "raised up to 512; all-mpnet-base-v2 itself uses 384)" % self.max_seq_length)
             self._warned_truncation = True
         cat = lambda k: torch.cat([r[k].reshape(1, -1).to(torch.long) for r in rows], 0)
         return {"input_ids": cat("input_ids"), "attention_mask": cat("attention_mask"), "token_type_ids": cat("token_type_ids")}
@@ -214,10 +216,10 @@ class SentenceTransformer(nn.Module):
         att = features.get("attention_mask", features.get("attention_masks")).to(dev)
         tt = features.get("token_type_ids")
         B, S = ids.shape
-        Bp = m._padded_batch(B, S)
+        Bp, S = m._padded_shape(B, S)
         c = SimpleNamespace(B=B, S=S, Bp=Bp)
-        c.ids, c.att = m._prep_ids(ids, Bp), m._prep_ids(att, Bp)
-        c.tt = None if tt is None else m._prep_ids(tt.to(dev), Bp)
+        c.ids, c.att = m._prep_ids(ids, Bp, S, m.cfg.pad_id), m._prep_ids(att, Bp, S)
+        c.tt = None if tt is None else m._prep_ids(tt.to(dev), Bp, S)
         lens = features.get("seq_lengths")
         if lens is None:
             lens = att.sum(1).tolist()                        # host list (one read-back; loaders that know the lengths pass them)

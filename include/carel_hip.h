@@ -32,7 +32,7 @@ extern "C" {
 #define CAREL_ERR_HIP (-3)    /* a HIP runtime call or launch failed    */
 
 /* ABI version of this header; carel_abi_version() must return the same number. */
-#define CAREL_ABI_VERSION 8
+#define CAREL_ABI_VERSION 9
 
 int carel_abi_version(void);
 /* Checks that `device` is a gfx950 part and fills the library's only per-device state, immutable afterwards: the 20-KiB GELU table of
@@ -231,7 +231,11 @@ int carel_colsum_bf16(const void* x_bf16, int64_t ld, int64_t rows, int32_t n, v
                       void* partials, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Self-attention of one encoder layer, all (sample, head) pairs; S in {32,64,96,128}, 12 heads x 64.
+ * Self-attention of one encoder layer, all (sample, head) pairs; S a multiple of 32 in [32, 512], 12 heads x 64.
+ * S <= 128: one workgroup per (sample, head), all of K and V in LDS (attention.hip).  S > 128 (ABI 9): flash-style kernels
+ * (attention_long.hip): the forward walks 128-key blocks with an online softmax; the backward runs a dQ pass over 128-query blocks
+ * and a dK / dV pass over 128-key blocks (no atomics: every gradient bit-reproducible) and needs `workspace`.  With dropout on,
+ * batch * 12 * S * S + drop_idx_offset must not exceed 2^32 (the element index is 32-bit; S = 512: about 1 365 samples per call).
  * Replaces transformers BertSelfAttention.forward after the q/k/v projections (eager attention:
  * softmax(QK^T/8 + (1-mask)*finfo.min) -> dropout -> PV) and its backward.
  * qkv / dqkv: bf16 [B*S, 2304] = q | k | v.  ctx / dctx: bf16 [B*S, 768].  lse: f32 [B, 12, S].
@@ -253,14 +257,19 @@ typedef struct carel_attn_args {
   /* MPNet relative-position bias (transformers MPNetAttention: attention_scores += position_bias; the encoder of
    * en_ec_sentence_transformer.py:22): f32 [heads][256], entry 127 + (key position - query position), made from the learned
    * [32 buckets][heads] table by carel_relpos_expand; NULL = no bias (BERT / RoBERTa). */
-  const void* rel_bias_dist;
-  void* d_rel_bias_dist;       /* bwd, required with rel_bias_dist: f32 [batch * heads][256], row (sample, head) ADDED to by that workgroup alone
+  const void* rel_bias_dist;   /* S > 128: f32 [heads][1024], entry 511 + (key - query) (entry 1023 unused), by carel_relpos_expand_span */
+  void* d_rel_bias_dist;       /* bwd, required with rel_bias_dist: f32 [batch * heads][256] (S > 128: [batch * heads][1024], entry as above), row (sample, head) ADDED to by that workgroup alone
                                   (no atomics: bit-reproducible); the caller zeroes it once per step -- every layer adds to it -- and folds
                                   it into the table gradient with carel_relpos_reduce */
   int32_t q_rows;              /* ABI 6.  0 = every query row; 32 / 64 / 96: only the first q_rows positions of every sample are queries --
                                   forward: ctx / lse rows past them are NOT written; backward: dctx rows past them are taken as zero and
                                   their dQ rows are written as zeros.  Exact where nothing downstream reads the other rows: the encoder's
                                   last layer when only [CLS] (position 0) is read after it (carel_encoder_args.n_cls) */
+  /* ABI 9.  bwd with S > 128: carel_attention_bwd_workspace_bytes(batch, seq_len, rel_bias_dist != NULL) bytes of device memory
+   * (f32 delta = rowsum(dO * O) [batch * heads * S], then with the bias its gradient partials [batch * heads][S/128 rounded up][1024]);
+   * contents need not be kept between calls.  Unused (may be NULL / 0) for S <= 128 and in the forward. */
+  void* workspace;
+  int64_t workspace_bytes;
 } carel_attn_args;
 
 int carel_attention_fwd(const carel_attn_args* args, void* stream);
@@ -268,6 +277,13 @@ int carel_attention_bwd(const carel_attn_args* args, void* stream);
 /* bucket: int32 [256], bucket[i] = relative_position_bucket(i - 127) (entry 255 unused), computed by the caller */
 int carel_relpos_expand(const void* table_f32_32xH, const void* bucket, void* dist_f32_Hx256, void* stream);
 int carel_relpos_reduce(const void* ddist_f32_BHx256, int32_t batch, const void* bucket, void* dtable_f32_32xH, int32_t accumulate, void* stream);
+/* ABI 9: 0 for seq_len <= 128 */
+int64_t carel_attention_bwd_workspace_bytes(int32_t batch, int32_t seq_len, int32_t with_rel);
+/* ABI 9: the same for a span of 256 (S <= 128; the bits of the two calls above) or 1024 (S > 128): bucket int32 [span],
+ * bucket[i] = relative_position_bucket(i - (span/2 - 1)) (entry span - 1 unused); dist f32 [H][span]; ddist f32 [batch * H][span] */
+int carel_relpos_expand_span(const void* table_f32_32xH, const void* bucket, void* dist_f32_Hxspan, int32_t span, void* stream);
+int carel_relpos_reduce_span(const void* ddist_f32_BHxspan, int32_t batch, const void* bucket, void* dtable_f32_32xH, int32_t accumulate,
+                             int32_t span, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Whole-encoder orchestration over caller-owned buffers.  Replaces `self.encoder(...)` (ref :202-206;
@@ -285,9 +301,15 @@ int carel_relpos_reduce(const void* ddist_f32_BHx256, int32_t batch, const void*
  *             (bit-reproducible) if the last forward that wrote keys into this scratch had the same act, input_ids, tok_row and
  *             row count and no later forward ran on that act.  Otherwise (a forward with scratch = NULL or with other ids, any
  *             forward in between on the same act) it falls back to float atomics: correct, not bit-reproducible.  The record is kept
- *             on the host by pointer: rewriting input_ids in place between forward and backward breaks the pairing unnoticed
+ *             on the host by pointer: rewriting input_ids in place between forward and backward breaks the pairing unnoticed.
+ *             seq_len > 128 (ABI 9): the scratch also holds the long-sequence attention backward's workspace
+ *             (carel_attention_bwd_workspace_bytes with the bias partials); a dense long batch passes 8 192 rows from B*S = 8 320 on
+ *             (e.g. B = 17 at S = 512), and its embedding gradients then take the atomic path above
  *   dx      : f32 [B*S, 768]; in: d(loss)/d(last hidden state); carried down through the layers
- * Constraints: hidden 768, 12 heads, intermediate 3072, seq_len in {32,64,96,128}, B*S % 128 == 0.
+ * Constraints: hidden 768, 12 heads, intermediate 3072, seq_len a multiple of 32 in [32, 512] (ABI 9; 160 .. 512 run the flash-style
+ * attention kernels, 32 .. 128 the one-workgroup-per-(sample, head) ones), B*S % 128 == 0; carel_embed_ln_fwd (the embeddings) also
+ * needs seq_len <= max_pos (BERT) or <= max_pos - pad_id - 1 (RoBERTa / MPNet: position ids from pad_id + 1).  carel_encoder_forward_f32
+ * stays at seq_len <= 128.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct carel_layer_params {
   const void* qkv_w; const void* qkv_b;     /* bf16 [2304,768], f32 [2304] */
