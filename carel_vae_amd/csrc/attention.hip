@@ -203,7 +203,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams p) {
   for (int kt = 0; kt < 4; ++kt) {
     if (kt < nkt) {
 #pragma unroll
-      for (int r = 0; r < 16; r += 2) {          // keys acc32_row(r), acc32_row(r + 1) are an aligned pair: one hash (ebase, S and the offset are even)
+      for (int r = 0; r < 16; r += 2) {          // keys acc32_row(r), acc32_row(r + 1) are an aligned pair: one hash (ebase, S and the offset are even: attn_prepare)
         const float e0 = __builtin_amdgcn_exp2f(x[kt][r] - m), e1 = __builtin_amdgcn_exp2f(x[kt][r + 1] - m);
         lsum += e0; lsum += e1;
         float d0 = 1.0f, d1 = 1.0f;
@@ -474,6 +474,13 @@ static int attn_prepare(const carel_attn_args* a, AttnParams* p, const char* who
   p->qlim = a->q_rows >= a->seq_len ? 0 : a->q_rows;
   if (bwd && p->rel && !p->drel) return set_error(CAREL_ERR_ARG, "%s: rel_bias_dist needs d_rel_bias_dist in the backward", who);
   p->drop = make_dropout(a->drop_seed, a->drop_site, a->drop_p, a->drop_idx_offset);
+  // both kernel families hash whole pairs of elements starting at an even index (the element index of key 0 is even when the offset is):
+  // an odd offset would pair every decision differently from carel_common.h's dropout_mult
+  if (p->drop.thresh != 0 && (a->drop_idx_offset & 1u))
+    return set_error(CAREL_ERR_ARG, "%s: drop_idx_offset must be even with dropout on (got %u)", who, a->drop_idx_offset);
+  if (p->drop.thresh != 0 && (uint64_t)a->batch * NH * (uint64_t)a->seq_len * a->seq_len + a->drop_idx_offset > 4294967296ull)
+    return set_error(CAREL_ERR_SHAPE, "%s: the dropout element index ((b*12 + h)*S + q)*S + k + drop_idx_offset would wrap 32 bits "
+                     "(batch %d, seq_len %d, offset %u): split the call", who, a->batch, a->seq_len, a->drop_idx_offset);
   return CAREL_OK;
 }
 

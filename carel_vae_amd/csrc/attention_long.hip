@@ -544,7 +544,8 @@ extern "C" int64_t carel_attention_bwd_workspace_bytes(int32_t batch, int32_t se
 }
 
 namespace carel {
-// called by attention.hip for seq_len > 128 (its checks have run: heads, head_dim, batch, tensors, q_rows, dropout)
+// called by attention.hip for seq_len > 128 (its checks have run: heads, head_dim, batch, tensors, q_rows, the dropout offset and
+// the 32-bit element index)
 int attn_long_prepare(const carel_attn_args* a, Params* p, const char* who, bool bwd) {
   p->qkv = (const bf16_t*)a->qkv; p->att_mask = (const long*)a->attention_mask; p->ctx = (bf16_t*)a->ctx;
   p->lse = (float*)a->lse; p->dctx = (const bf16_t*)a->dctx; p->dqkv = (bf16_t*)a->dqkv;
@@ -552,9 +553,6 @@ int attn_long_prepare(const carel_attn_args* a, Params* p, const char* who, bool
   p->rel = (const float*)a->rel_bias_dist; p->drel = (float*)a->d_rel_bias_dist;
   p->qlim = a->q_rows >= a->seq_len ? 0 : a->q_rows;
   p->drop = make_dropout(a->drop_seed, a->drop_site, a->drop_p, a->drop_idx_offset);
-  if (p->drop.thresh != 0 && (uint64_t)a->batch * NH * (uint64_t)a->seq_len * a->seq_len + a->drop_idx_offset > 4294967296ull)
-    return set_error(CAREL_ERR_SHAPE, "%s: the dropout element index ((b*12 + h)*S + q)*S + k + drop_idx_offset would wrap 32 bits "
-                     "(batch %d, seq_len %d, offset %u): split the call", who, a->batch, a->seq_len, a->drop_idx_offset);
   p->nqb = n_blocks(a->seq_len); p->nkb = p->nqb;
   if (p->qlim) p->nqb = n_blocks(p->qlim);
   p->delta = nullptr; p->drel_part = nullptr;

@@ -235,7 +235,10 @@ int carel_colsum_bf16(const void* x_bf16, int64_t ld, int64_t rows, int32_t n, v
  * S <= 128: one workgroup per (sample, head), all of K and V in LDS (attention.hip).  S > 128 (ABI 9): flash-style kernels
  * (attention_long.hip): the forward walks 128-key blocks with an online softmax; the backward runs a dQ pass over 128-query blocks
  * and a dK / dV pass over 128-key blocks (no atomics: every gradient bit-reproducible) and needs `workspace`.  With dropout on,
- * batch * 12 * S * S + drop_idx_offset must not exceed 2^32 (the element index is 32-bit; S = 512: about 1 365 samples per call).
+ * drop_idx_offset must be even (the kernels hash whole pairs of elements) and batch * 12 * S * S + drop_idx_offset must not exceed 2^32
+ * (the element index is 32-bit; S = 512: about 1 365 samples per call); both are refused with an error before any launch.
+ * A sample with no attended key (all-zero mask) gets HF's uniform row in the forward, but exact zeros in all of its dQ / dK / dV rows
+ * in the backward, where HF autograd would give nonzero dK / dV (no input of the encoder has such a sample).
  * Replaces transformers BertSelfAttention.forward after the q/k/v projections (eager attention:
  * softmax(QK^T/8 + (1-mask)*finfo.min) -> dropout -> PV) and its backward.
  * qkv / dqkv: bf16 [B*S, 2304] = q | k | v.  ctx / dctx: bf16 [B*S, 768].  lse: f32 [B, 12, S].
@@ -249,7 +252,7 @@ typedef struct carel_attn_args {
   const void* dctx;            /* bwd in  */
   void* dqkv;                  /* bwd out */
   int32_t batch, seq_len, heads, head_dim;
-  uint32_t drop_seed, drop_site, drop_idx_offset;
+  uint32_t drop_seed, drop_site, drop_idx_offset;   /* drop_idx_offset: even when drop_p > 0 */
   float drop_p;
   /* token packing: sample b owns rows [cu_seqlens[b], cu_seqlens[b+1]) of qkv/ctx/dctx/dqkv and attends to exactly
    * those (attention_mask is ignored); seq_len stays the ORIGINAL padded length (dropout index, lse stride). */

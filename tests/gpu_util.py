@@ -1,5 +1,6 @@
 """Helpers for the -m gpu tests: all calls go through the C ABI (carel_vae_amd._lib)."""
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -43,3 +44,105 @@ def gemm(A, B, form, epi, M, N, K, splits=1, out_bf16=None, out2_bf16=None, out_
 def rel_err(got: torch.Tensor, ref: torch.Tensor) -> float:
     got, ref = got.double().cpu(), ref.double().cpu()
     return float((got - ref).norm() / max(ref.norm().item(), 1e-30))
+
+
+# ------------------------------------------------------------------------------------------------ attention: fp64 reference, block metric
+ATT_NH, ATT_HD = 12, 64
+ATT_H = ATT_NH * ATT_HD
+
+
+def attn_keep(B, S, drop, device="cuda"):
+    """Dropout multipliers [B, 12, S, S] (0 or 1/(1-p), float64) of the attention probabilities from oracle.dropout_keep: element
+    ((b*12 + h)*S + q)*S + k + offset as a uint32 (wrapping); None for p <= 0."""
+    from oracle import carel_oracle as O
+    seed, site, off, p = drop
+    if p <= 0:
+        return None
+    idx = (np.arange(B * ATT_NH * S * S, dtype=np.uint64) + np.uint64(off)).astype(np.uint32)
+    keep = torch.from_numpy(O.dropout_keep(seed, site, idx, p)).to(device)
+    return keep.view(B, ATT_NH, S, S).double() / (1.0 - p)
+
+
+def _mpnet_bias(tab, n):
+    """[12, n, n]: tab[bucket(key - query), head] (transformers MPNetAttention position_bias) from the [32, 12] table."""
+    from oracle import carel_oracle as O
+    pos = torch.arange(n)
+    return tab[O.mpnet_relative_position_bucket(pos[None, :] - pos[:, None]).to(tab.device)].permute(2, 0, 1)
+
+
+def _eager_fp64(qkv_rows, b, n, add, keep, bias):
+    x = qkv_rows.double().view(b, n, 3, ATT_NH, ATT_HD).requires_grad_(True)
+    q, k, v = (x[:, :, i].transpose(1, 2) for i in range(3))                 # [b, 12, n, 64]
+    s = q @ k.transpose(-1, -2) / math.sqrt(ATT_HD)
+    if bias is not None:
+        s = s + bias
+    if add is not None:
+        s = s + add
+    lse = torch.logsumexp(s, dim=-1)
+    pr = torch.softmax(s, dim=-1)
+    if keep is not None:
+        pr = pr * keep
+    return x, (pr @ v).transpose(1, 2).reshape(b * n, ATT_H), lse
+
+
+def attn_ref_fp64(qkv, dctx, B, S, mask=None, cu=None, drop=(0, 0, 0, 0.0), table=None):
+    """HF eager attention in float64 on the kernels' own bf16 inputs: softmax(QK^T/8 [+ MPNet bias] + (1 - mask) * finfo(float32).min)
+    -> dropout (attn_keep) -> PV, and its autograd backward for the upstream gradient dctx.  Packed (cu_seqlens, int list or tensor
+    [B+1]): one call per sample on its own rows, no mask term.  table: the MPNet [32, 12] bias table (None = no bias).
+    Returns (ctx [rows, 768], lse [B, 12, S] (nan past a packed sample), dqkv [rows, 2304], d table [32, 12] or None), float64 on
+    qkv's device; rows of qkv outside every sample stay 0."""
+    dev, rows = qkv.device, qkv.shape[0]
+    keep = attn_keep(B, S, drop, dev)
+    tab = None if table is None else table.detach().to(dev).double().requires_grad_(True)
+    ctx = torch.zeros((rows, ATT_H), dtype=torch.float64, device=dev)
+    dqkv = torch.zeros((rows, 3 * ATT_H), dtype=torch.float64, device=dev)
+    lse = torch.full((B, ATT_NH, S), float("nan"), dtype=torch.float64, device=dev)
+    if cu is None:
+        add = None if mask is None else ((1.0 - mask.double()) * torch.finfo(torch.float32).min)[:, None, None, :]
+        x, c, l = _eager_fp64(qkv[:B * S], B, S, add, keep, None if tab is None else _mpnet_bias(tab, S))
+        c.backward(dctx[:B * S].double())
+        ctx[:B * S], lse[:], dqkv[:B * S] = c.detach(), l.detach(), x.grad.reshape(B * S, 3 * ATT_H)
+    else:
+        cu = [int(v) for v in cu]
+        for b in range(B):
+            r0, n = cu[b], cu[b + 1] - cu[b]
+            if n == 0:
+                continue
+            x, c, l = _eager_fp64(qkv[r0:r0 + n], 1, n, None, None if keep is None else keep[b:b + 1, :, :n, :n],
+                                  None if tab is None else _mpnet_bias(tab, n))
+            c.backward(dctx[r0:r0 + n].double())
+            ctx[r0:r0 + n], lse[b, :, :n], dqkv[r0:r0 + n] = c.detach(), l.detach()[0], x.grad.reshape(n, 3 * ATT_H)
+    return ctx, lse, dqkv, (None if tab is None else tab.grad)
+
+
+def block_rel_err(got, ref, segs, floor=0.05):
+    """Worst relative error over the (sample, head, 32-row tile) blocks of a [rows, 12 * 64] tensor; segs = [(first row, rows)] of the
+    samples, tiles counted from each sample's first row (the last one partial).  A block's error is ||got - ref|| / max(||ref||,
+    floor * median of the tensor's nonzero block norms): a block that is (nearly) zero in exact arithmetic is measured against the
+    typical block instead of itself.  Returns ((error, (sample, tile, head))) of the blocks at or above that floor and of those below
+    it, separately: below it the attention backward's error is that of delta = rowsum(dO * O) taken from the bf16 context rows (a
+    query whose softmax sits on one key has an exact dQ of 0), which sets a looser bound than the other blocks need."""
+    got = got.to(ref.device).double().reshape(-1, ATT_NH, ATT_HD)
+    ref = ref.double().reshape(-1, ATT_NH, ATT_HD)
+    rows, ids, where = [], [], []
+    for s, (r0, n) in enumerate(segs):
+        r = torch.arange(n, device=ref.device)
+        rows.append(r0 + r)
+        ids.append(len(where) + r // 32)
+        where += [(s, t) for t in range((n + 31) // 32)]
+    rows, ids = torch.cat(rows), torch.cat(ids)
+    d2 = torch.zeros((len(where), ATT_NH), dtype=torch.float64, device=ref.device)
+    r2 = torch.zeros_like(d2)
+    d2.index_add_(0, ids, ((got[rows] - ref[rows]) ** 2).sum(-1))
+    r2.index_add_(0, ids, (ref[rows] ** 2).sum(-1))
+    dn, rn = d2.sqrt(), r2.sqrt()
+    nz = rn[rn > 0]
+    med = float(nz.median()) if nz.numel() else 0.0
+    lim = max(floor * med, 1e-30)
+    err = dn / rn.clamp(min=lim)
+    out = []
+    for sel in (rn >= lim, rn < lim):
+        e = torch.where(sel, err, torch.zeros_like(err))
+        i = int(e.argmax())
+        out.append((float(e.flatten()[i]), where[i // ATT_NH] + (i % ATT_NH,)))
+    return tuple(out)
