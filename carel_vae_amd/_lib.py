@@ -164,6 +164,15 @@ class ViArgs(C.Structure):
                 ("loss_out", C.c_void_p), ("d_net", C.c_void_p * 8), ("dz", C.c_void_p)]
 
 
+class GanArgs(C.Structure):
+    """carel_gan_args (include/carel_hip.h)."""
+    _fields_ = [("z", C.c_void_p), ("batch", C.c_int32), ("ec_dim", C.c_int32), ("emo_labels", C.c_void_p), ("cau_labels", C.c_void_p),
+                ("disc_w", C.c_void_p * 2), ("disc_b", C.c_void_p * 2), ("label_smoothing", C.c_float), ("epsilon", C.c_float),
+                ("drop_p", C.c_float), ("drop_seed", C.c_uint32), ("drop_row_offset", C.c_uint32), ("vae_loss_in", C.c_void_p),
+                ("w_entropy", C.c_float), ("terms", C.c_void_p), ("g_loss_w", C.c_void_p * 2), ("g_loss_b", C.c_void_p * 2),
+                ("g_ent_w", C.c_void_p * 2), ("g_ent_b", C.c_void_p * 2)]
+
+
 class EnTailArgs(C.Structure):
     """carel_en_tail_args (include/carel_hip.h)."""
     _fields_ = [("batch", C.c_int32), ("seq_len", C.c_int32), ("hidden", C.c_int32), ("ec_dim", C.c_int32), ("con_dim", C.c_int32),
@@ -257,6 +266,7 @@ SIGNATURES = {
     "carel_tail_backward_dz": (C.c_int, [C.POINTER(TailArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
     "carel_vi_aprx": (C.c_int, [C.POINTER(ViArgs), C.c_void_p]),
     "carel_vi_upper": (C.c_int, [C.POINTER(ViArgs), C.c_void_p]),
+    "carel_gan_disc": (C.c_int, [C.POINTER(GanArgs), C.c_void_p]),
     "carel_scale_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "carel_tail_pair_dead_offset": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "carel_pair_probs": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

@@ -98,6 +98,8 @@ class DataParallel:
     optimiser calls).  Every rank must call forward with the same local batch size."""
 
     def __init__(self, model, group=None, global_batch_terms=True, wire_dtype=None, embed_chunks=4, overlap_wgrad=False):
+        if getattr(model, "_gan", False):
+            raise L.CarelError("opt.disentangle == 'gan' is not supported under DataParallel (the adversaries' gradients are not reduced)")
         if not dist.is_initialized():
             raise RuntimeError("torch.distributed must be initialised (init_process_group) before DataParallel")
         if getattr(model, "adapter", "false") != "false":

@@ -34,6 +34,23 @@ def make_opt(**kw):
     return SimpleNamespace(**d)
 
 
+# drl_classifier_ec_gan.py:30-57: the parser defaults of the adversarial (GAN) ablation; the two heads share ec_mul_loss_weight
+GAN_OPT = dict(language="zh", max_len=128, ec_num_class=1, e_num_class=1, c_num_class=1, pair_num_class=1, ec_dim=24, con_dim=384,
+               pair_bow_dim=23771, bert_dim=768, kl_ann_iterations=20000, epochs=10, batch_size=64, ec_kl_lambda=0.03, con_kl_lambda=0.03,
+               label_smoothing=0.1, ecce_adv_loss_weight=1.0, ec_mul_loss_weight=10.0, pair_mul_loss_weight=25.0, dropout=0.5, epsilon=1e-8,
+               adv_lr=0.003, vae_lr=1e-5, self_iteration=50, self_epochs=10, self_strategy="random",
+               best_model_path="ECPE_model/best_drl_model", model_id="carel-gan", disentangle="gan", emotion_head="bce")
+GAN_DISCS = ("ec_disc", "ce_disc")          # get_params() order (:310-317)
+
+
+def make_gan_opt(**kw):
+    """The argparse namespace of drl_classifier_ec_gan.py (:30-57) with its defaults, plus the two switches that select that script's
+    model here: disentangle="gan" and the one-logit BCE emotion head (e_num_class / c_num_class mirror its ec_num_class = 1)."""
+    d = dict(GAN_OPT)
+    d.update(kw)
+    return SimpleNamespace(**d)
+
+
 REL_KEY = "encoder.encoder.relative_attention_bias.weight"
 
 
@@ -226,6 +243,25 @@ class _TrainLoss(torch.autograd.Function):
         return None, None, None
 
 
+class _GanLosses(torch.autograd.Function):
+    """Whole-step forward of the GAN ablation returning (ec_disc_loss, ce_disc_loss, vae_and_classifier_loss); each backward call
+    receives the upstream gradients of the losses it was started from (None for the others), in the manner of the three-space
+    model's _EnLosses: the losses are roots of the graph, every gradient image was produced by the forward kernels."""
+
+    @staticmethod
+    def forward(ctx, anchor, model, call):
+        ctx.model, ctx.call = model, call
+        ctx.set_materialize_grads(False)
+        model._run_forward(call, training=True)
+        t = call.gan_terms
+        return t[0].clone(), t[1].clone(), t[4].clone()
+
+    @staticmethod
+    def backward(ctx, g_ec, g_ce, g_vae):
+        ctx.model._run_backward_gan(ctx.call, (g_ec, g_ce, g_vae))
+        return None, None, None
+
+
 class _AprxLoss(torch.autograd.Function):
     """`get_ec_aprx_loss` of drl_classifier_ec_vi.py:422-427: loss of the approximation network p(e|c) on the sampled
     embeddings; its backward fills ONLY the eight ec_mu / ec_log_var gradients.  (In the reference the term also sends a
@@ -398,6 +434,8 @@ class DrlClassifier(nn.Module):
         self.encoder = CarelEncoder(self.cfg)
         self._aprx_names = []
         self._adapter_names = []
+        self._disc_names = []               # the two adversaries of opt.disentangle == "gan" (fp32 only, own optimisers)
+        self._gan = getattr(opt, "disentangle", "mmd") == "gan"
         self._has_pair_skip = True          # the pair head is frozen for a step whose pair loss was replaced by 0 (ref :510-511)
         self.strict_pair_skip = False       # True: also leave its .grad None on such a step (for stock torch optimisers; one host read per step)
         self._build_heads(opt)
@@ -436,6 +474,14 @@ class DrlClassifier(nn.Module):
         self.emotion_log_var = _Holder((opt.ec_dim, H))
         self.cause_mu = _Holder((opt.ec_dim, H))
         self.cause_log_var = _Holder((opt.ec_dim, H))
+        if self._gan:                       # registered where drl_classifier_ec_gan.py builds them (:168-169): state_dict keys in its order
+            counts = [getattr(opt, n, 1) for n in ("e_num_class", "c_num_class", "pair_num_class", "ec_num_class")]
+            if getattr(opt, "emotion_head", "ce") != "bce" or any(c != 1 for c in counts):
+                raise L.CarelError("opt.disentangle == 'gan' is the one-logit model of drl_classifier_ec_gan.py: it needs "
+                                   "opt.emotion_head == 'bce' and e_num_class = c_num_class = pair_num_class = ec_num_class = 1; got "
+                                   "emotion_head %r, class counts %r" % (getattr(opt, "emotion_head", "ce"), counts))
+            self.ec_disc, self.ce_disc = _Holder((1, opt.ec_dim)), _Holder((1, opt.ec_dim))
+            self._disc_names = [g + t for g in GAN_DISCS for t in (".weight", ".bias")]
         self.emotion_classifier = _Holder((opt.e_num_class, opt.ec_dim))
         self.cause_classifier = _Holder((opt.c_num_class, opt.ec_dim))
         self.pair_classifier = _Holder((opt.pair_num_class, opt.ec_dim * 2))
@@ -457,6 +503,7 @@ class DrlClassifier(nn.Module):
         self._pair_range_names = ["pair_classifier.weight", "pair_classifier.bias"]
         order += self._pair_range_names
         n_opt_names = len(order)
+        order += self._disc_names            # gan: [vae group | ec_disc | ce_disc | latent heads], each optimiser group one contiguous range
         order += ["emotion_mu.weight", "emotion_mu.bias", "emotion_log_var.weight", "emotion_log_var.bias",
                   "cause_mu.weight", "cause_mu.bias", "cause_log_var.weight", "cause_log_var.bias"]
         order += self._adapter_names         # frozen like the latent heads (absent from get_params() in the reference, :460)
@@ -511,6 +558,14 @@ class DrlClassifier(nn.Module):
         self._enc_ws = {}
         self._pair_lo = offs[self._pair_range_names[0]]
         self._pair_hi = offs[self._pair_range_names[1]] + named[self._pair_range_names[1]].numel()
+        if getattr(self, "_gan", False):
+            end = lambda k: offs[k] + ((named[k].numel() + 63) & ~63)        # noqa: E731
+            self._group_ranges = {"vae": (0, self._n_opt)}
+            for g in GAN_DISCS:
+                self._group_ranges[g] = (offs[g + ".weight"], end(g + ".bias"))
+            self._disc_lo, self._disc_hi = self._group_ranges[GAN_DISCS[0]][0], self._group_ranges[GAN_DISCS[-1]][1]
+            # gradient images of the discriminator range for unit upstream gradients: [0] own loss, [1] entropy term (carel_gan_disc)
+            self._disc_img = [torch.zeros(self._disc_hi - self._disc_lo, device=dev) for _ in range(2)] if dev.type == "cuda" else None
 
     def _apply(self, fn, *a, **kw):
         r = super()._apply(fn, *a, **kw)
@@ -534,7 +589,21 @@ class DrlClassifier(nn.Module):
                  list(self.pair_classifier.parameters()))
         if self._aprx_names:
             return list(self.ec_mu.parameters()) + list(self.ec_log_var.parameters()), other
+        if self._gan:            # (ec_disc_params, ce_disc_params, other_params), drl_classifier_ec_gan.py:302-317
+            return list(self.ec_disc.parameters()), list(self.ce_disc.parameters()), other
         return other
+
+    def make_fused_optimizers(self, adv_lr=None, vae_lr=None, fuse_into_backward=False):
+        """opt.disentangle == "gan": the three optimisers of drl_classifier_ec_gan.py's script body (:903-908) as HIP kernels over the flat
+        buffer, in get_params() order: RMSprop(adv_lr) for ec_disc and for ce_disc, Adam(vae_lr) for the rest."""
+        if not self._gan:
+            raise L.CarelError("make_fused_optimizers() belongs to opt.disentangle == 'gan' (use FusedAdam(model) otherwise)")
+        adv_lr = self.opt.adv_lr if adv_lr is None else adv_lr
+        vae_lr = self.opt.vae_lr if vae_lr is None else vae_lr
+        groups = self.get_params()
+        opts = [FusedRMSprop(self, lr=adv_lr, param_range=self._group_ranges[g], params=groups[i]) for i, g in enumerate(GAN_DISCS)]
+        opts.append(FusedAdam(self, lr=vae_lr, param_range=self._group_ranges["vae"], params=groups[2], fuse_into_backward=fuse_into_backward))
+        return tuple(opts)
 
     def _aprx_weights(self):
         if not self._aprx_names:
@@ -563,7 +632,7 @@ class DrlClassifier(nn.Module):
                                "implementation of the step path (no CPU fallback)." % (None if self._flat is None else self._flat.device))
 
     def _versions(self):
-        aprx = set(self._aprx_names)         # fp32 only: an update of the approximation net never stales the bf16 shadow
+        aprx = set(self._aprx_names) | set(self._disc_names)   # fp32 only: an update of the approximation net / adversaries never stales the bf16 shadow
         return sum(p._version for k, p in self._named.items() if k not in aprx)
 
     def _refresh_shadow(self):
@@ -856,6 +925,12 @@ class DrlClassifier(nn.Module):
         c.pack = self._pack_info(c.att, B, Bp, S, seq_lengths)
         if self.adapter != "false" and self._dp is not None:
             raise L.CarelError("sentence adapters are not supported under DataParallel")
+        if self._gan:
+            if self._dp is not None:
+                raise L.CarelError("opt.disentangle == 'gan' is not supported under DataParallel")
+            c.labels["emo_f"] = emotion_labels.to(dev, f32).reshape(-1).contiguous()     # the adversaries score float labels (:83, :133)
+            if c.labels["emo_f"].numel() != B or c.labels["cau"].numel() != B:
+                raise L.CarelError("emotion_labels and cause_labels must hold one value per pair")
         key = ("tail", B, S)
         buf = self._ws.get(key)
         if buf is None:
@@ -950,8 +1025,59 @@ class DrlClassifier(nn.Module):
             self._dp.fill_global(ta, c)                  # all-gather z, all-reduce label sum
         ta.serial = 0 if self.overlap_wgrad else 1       # side stream allowed: the loss kernel runs beside the decoder passes
         ops.tail_losses(ta)
+        if self._gan:                                    # the two adversaries on the z the tail has written; terms[4] = the script's vae loss
+            c.gan_terms = self._gan_disc(c, drop)
         c.ea, c.ta, c.ws = ea, ta, ws
         c.keep = (W, G, xl)
+
+    def _gan_disc(self, c, drop):
+        key = ("gan_terms", c.B, c.S)
+        terms = self._ws.get(key)
+        if terms is None:
+            terms = self._ws[key] = torch.zeros(8, device=self._flat.device, dtype=torch.float32)
+
+        def img(i, k):
+            o = self._offs[k] - self._disc_lo
+            return self._disc_img[i][o:o + self._named[k].numel()]
+        w = [self._named[g + ".weight"].data for g in GAN_DISCS]
+        b = [self._named[g + ".bias"].data for g in GAN_DISCS]
+        ops.gan_disc(c.buf.z, c.labels["emo_f"], c.labels["cau"], w, b, self.opt, terms,
+                     [img(0, g + ".weight") for g in GAN_DISCS], [img(0, g + ".bias") for g in GAN_DISCS],
+                     [img(1, g + ".weight") for g in GAN_DISCS], [img(1, g + ".bias") for g in GAN_DISCS],
+                     drop=drop, vae_loss_in=c.buf.terms[8:9])
+        return terms
+
+    def _group_has_grad(self, g):
+        """Does a backward call into group g accumulate?  An adversary's range is written as a whole, so both of its parameters count:
+        it accumulates only when both hold a gradient (as FusedRMSprop.step steps only then); a half-cleared group is overwritten."""
+        if g == "vae":
+            return self._named["encoder.embeddings.word_embeddings.weight"].grad is not None
+        return all(self._named[g + t].grad is not None for t in (".weight", ".bias"))
+
+    def _run_backward_gan(self, c, grads):
+        """Backward of the (ec_disc_loss, ce_disc_loss, vae_and_classifier_loss) tuple (drl_classifier_ec_gan.py:784-802): a
+        discriminator loss adds its own image, scaled by its upstream gradient, into that discriminator's .grad; the vae loss runs the
+        encoder backward and adds ecce_adv_loss_weight x the entropy image into BOTH discriminators' .grad -- accumulating like torch."""
+        f32 = torch.float32
+        if self._grad_views is None:
+            self._grad_views = {k: self._grad_view(k) for k in self._order}
+
+        def share(group, image, g_dev):
+            lo, hi = self._group_ranges[group]
+            ops.axpy_(self._flat_grad[lo:hi], self._disc_img[image][lo - self._disc_lo:hi - self._disc_lo], g_dev, self._group_has_grad(group))
+            for t in (".weight", ".bias"):
+                self._named[group + t].grad = self._grad_views[group + t]
+
+        for i, group in enumerate(GAN_DISCS):
+            if grads[i] is not None:
+                share(group, 0, grads[i].to(f32).reshape(1).contiguous())
+        if grads[2] is not None:
+            go = grads[2].to(f32).reshape(1).contiguous()
+            w = float(self.opt.ecce_adv_loss_weight)
+            ge = go if w == 1.0 else go * w
+            for group in GAN_DISCS:
+                share(group, 1, ge)
+            self._run_backward(c, go, None)
 
     def _run_backward(self, c, grad_out, grad_z=None):
         lib = L.load()
@@ -960,6 +1086,8 @@ class DrlClassifier(nn.Module):
         first = named[self._order[0]]
         accumulate = first.grad is not None
         prev = self._flat_grad.clone() if accumulate else None
+        if accumulate and self._gan:         # the adversaries' range is not rewritten below: it must not be added to itself
+            prev[self._disc_lo:self._disc_hi].zero_()
         go = grad_out.to(torch.float32).reshape(1).contiguous()      # device scalar, never read on the host
         ea = c.ea
         ea.dx = c.buf.dx_last.data_ptr()          # [Bp*S (or packed n_tokens), 768]; cleared + CLS rows written by the tail backward
@@ -1029,9 +1157,9 @@ class DrlClassifier(nn.Module):
     def _bind_grads(self):
         if self._grad_views is None:
             self._grad_views = {k: self._grad_view(k) for k in self._order}
-        skip = set(self._aprx_names) | set(self._adapter_names)
+        skip = set(self._aprx_names) | set(self._adapter_names) | set(self._disc_names)
         for k, p in self._named.items():
-            if k not in skip:               # the approximation net's gradients belong to _AprxLoss.backward; adapters get none (frozen)
+            if k not in skip:               # the approximation net's gradients belong to _AprxLoss.backward (the adversaries': _run_backward_gan); adapters get none (frozen)
                 p.grad = self._grad_views[k]
 
     # ------------------------------------------------------------------ public API (reference surface)
@@ -1045,6 +1173,12 @@ class DrlClassifier(nn.Module):
         self._last_call = c
         vi = bool(self._aprx_names)
         D = self.opt.ec_dim
+        if self._gan:            # drl_classifier_ec_gan.py:281: (ec_disc_loss, ce_disc_loss, vae_and_classifier_loss)
+            if torch.is_grad_enabled():
+                return _GanLosses.apply(self._flat.new_zeros((), requires_grad=True), self, c)
+            self._run_forward(c, training=False)
+            t = c.gan_terms
+            return t[0].clone(), t[1].clone(), t[4].clone()
         if torch.is_grad_enabled():
             anchor = self._flat.new_zeros((), requires_grad=True)
             loss, z = _TrainLoss.apply(anchor, self, c)
@@ -1077,6 +1211,10 @@ class DrlClassifier(nn.Module):
         lat = c.buf.lat.clone()
         out = {n: t[i] for i, n in enumerate(self.TERM_NAMES)}
         out.update(mu_e=lat[:, :D], lv_e=lat[:, D:2 * D], mu_c=lat[:, 2 * D:3 * D], lv_c=lat[:, 3 * D:], z=c.buf.z.clone())
+        if self._gan:            # "loss" stays the tail's own total; "vae_and_classifier_loss" adds the weighted entropies (:275-279)
+            g = c.gan_terms.clone()
+            out.update({n: g[i] for i, n in enumerate(ops.GAN_TERM_NAMES)})
+            out["vae_and_classifier_loss"] = g[4]
         if c.ad is not None:                 # the heads' inputs: emotion / cause adapter outputs (the pooler is not run)
             a = self._ws[("adapter", c.B, c.S)].out
             out.update(adapter_e=a[0].clone(), adapter_c=a[1].clone())
@@ -1155,14 +1293,18 @@ class FusedAdam:
 
     def __init__(self, model, lr=1e-5, betas=(0.9, 0.999), eps=1e-8, fuse_into_backward=False, param_range=None, params=None):
         """param_range / params (both or neither): a contiguous [lo, hi) slice of the flat buffer and the Parameters in
-        it, for models whose get_params() returns several optimiser groups (drl_classifier_en.py:357-376)."""
+        it, for models whose get_params() returns several optimiser groups (drl_classifier_en.py:357-376).
+        Without them on a model whose get_params() is a tuple (opt.disentangle "vi" / "gan"), the optimiser takes the LAST group, the
+        vae-and-classifier one; on a gan model its zero_grad() then clears that group only, like torch -- the same Adam optimiser that
+        model.make_fused_optimizers() builds as its third element."""
         model._require_cuda()
         self.model, self.lr, self.betas, self.eps = model, lr, betas, eps
         self.step_count = 0
         self._lo, self._hi = (0, model._n_opt) if param_range is None else param_range
-        self._clear_all = params is None      # the single-optimiser scripts: zero_grad() clears every .grad of the model
+        self._clear_all = params is None and not model._gan      # the single-optimiser scripts: zero_grad() clears every .grad of the model
         if params is None:
-            params = model.get_params() if not model._aprx_names else model.get_params()[1]
+            gp = model.get_params()              # several groups (vi: 2, gan: 3): the vae group is the last
+            params = gp[-1] if isinstance(gp, tuple) else gp
         self._params = list(params)
         self.exp_avg = torch.zeros(self._hi - self._lo, device=model._flat.device, dtype=torch.float32)
         self.exp_avg_sq = torch.zeros_like(self.exp_avg)
@@ -1266,3 +1408,34 @@ class FusedAdam:
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         fr = sd.get("pair_head_frozen_steps")
         self._skip_count = None if fr is None else fr.to(self.exp_avg.device, torch.float32).reshape(1).clone()
+
+
+class FusedRMSprop:
+    """`torch.optim.RMSprop(params, lr)` (torch defaults) over one contiguous range of the model's flat buffer; used through
+    zero_grad() / step() like the discriminator optimisers of drl_classifier_en.py (:919-947, :1056-1060) and drl_classifier_ec_gan.py (:784-802, :903-908)."""
+
+    def __init__(self, model, lr, param_range, params, alpha=0.99, eps=1e-8):
+        model._require_cuda()
+        self.model, self.lr, self.alpha, self.eps = model, lr, alpha, eps
+        self._lo, self._hi = param_range
+        self._params = list(params)
+        self.square_avg = torch.zeros(self._hi - self._lo, device=model._flat.device, dtype=torch.float32)
+        self.param_groups = [dict(params=self._params, lr=lr, alpha=alpha, eps=eps)]
+
+    def zero_grad(self, set_to_none=True):
+        for p in self._params:
+            p.grad = None
+
+    def step(self):
+        m = self.model
+        if any(p.grad is None for p in self._params):
+            return                                   # torch skips parameters without a gradient
+        L.check(L.load().carel_rmsprop_step(m._flat.data_ptr() + 4 * self._lo, m._flat_grad.data_ptr() + 4 * self._lo, self.square_avg.data_ptr(),
+                                            self._hi - self._lo, self.param_groups[0]["lr"], self.alpha, self.eps, L.current_stream()),
+                "carel_rmsprop_step")
+
+    def state_dict(self):
+        return dict(square_avg=self.square_avg, lr=self.lr)
+
+    def load_state_dict(self, sd):
+        self.square_avg.copy_(sd["square_avg"])

@@ -26,7 +26,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from . import data as _data
-from .drl_classifier import DrlClassifier as _Base, FusedAdam, H, _Call, _Holder, encoder_config
+from .drl_classifier import DrlClassifier as _Base, FusedAdam, FusedRMSprop, H, _Call, _Holder, encoder_config  # noqa: F401 (FusedRMSprop: re-exported)
 
 DEFAULT_OPT = dict(language="en", max_len=128, ec_num_class=1, pair_num_class=1, ec_dim=24, con_dim=384, pair_bow_dim=23771, bert_dim=768,
                    kl_ann_iterations=20000, epochs=10, batch_size=64, ec_kl_lambda=0.03, con_kl_lambda=0.03, label_smoothing=0.1,
@@ -116,37 +116,6 @@ class _EnLosses(torch.autograd.Function):
     def backward(ctx, *grads):
         ctx.model._run_backward_en(ctx.call, grads)
         return None, None, None
-
-
-class FusedRMSprop:
-    """`torch.optim.RMSprop(params, lr)` (torch defaults) over one contiguous range of the model's flat buffer; used through
-    zero_grad() / step() like the reference's discriminator optimisers (:919-947, :1056-1060)."""
-
-    def __init__(self, model, lr, param_range, params, alpha=0.99, eps=1e-8):
-        model._require_cuda()
-        self.model, self.lr, self.alpha, self.eps = model, lr, alpha, eps
-        self._lo, self._hi = param_range
-        self._params = list(params)
-        self.square_avg = torch.zeros(self._hi - self._lo, device=model._flat.device, dtype=torch.float32)
-        self.param_groups = [dict(params=self._params, lr=lr, alpha=alpha, eps=eps)]
-
-    def zero_grad(self, set_to_none=True):
-        for p in self._params:
-            p.grad = None
-
-    def step(self):
-        m = self.model
-        if any(p.grad is None for p in self._params):
-            return                                   # torch skips parameters without a gradient
-        L.check(L.load().carel_rmsprop_step(m._flat.data_ptr() + 4 * self._lo, m._flat_grad.data_ptr() + 4 * self._lo, self.square_avg.data_ptr(),
-                                            self._hi - self._lo, self.param_groups[0]["lr"], self.alpha, self.eps, L.current_stream()),
-                "carel_rmsprop_step")
-
-    def state_dict(self):
-        return dict(square_avg=self.square_avg, lr=self.lr)
-
-    def load_state_dict(self, sd):
-        self.square_avg.copy_(sd["square_avg"])
 
 
 class DrlClassifier(_Base):

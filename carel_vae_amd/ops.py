@@ -115,6 +115,9 @@ def kl_anneal_weight(iteration, opt):
     return 1.0
 
 
+DISENTANGLE_MODES = ("mmd", "hsic", "none", "vi", "gan")
+
+
 class TailBuffers:
     """Outputs + workspace of the tail calls for one (batch, ec_dim, bow_dim) shape."""
 
@@ -155,18 +158,24 @@ def tail_args(buf: TailBuffers, x_last, W, labels, eps_e, eps_c, opt, kl_weight,
         a.pair_labels, a.bow = labels["pair"].data_ptr(), labels["bow"].data_ptr()
     a.eps_e = None if eps_e is None else eps_e.data_ptr()
     a.eps_c = None if eps_c is None else eps_c.data_ptr()
-    a.w_mmd, a.w_emo, a.w_cau, a.w_pair = (opt.mmd_loss_weight, opt.emo_mul_loss_weight, opt.cau_mul_loss_weight,
-                                            opt.pair_mul_loss_weight)
+    if getattr(opt, "disentangle", "mmd") == "gan":      # drl_classifier_ec_gan.py:275-279: no statistic, one weight for both one-logit heads
+        a.w_mmd, a.w_emo, a.w_cau, a.w_pair = 0.0, opt.ec_mul_loss_weight, opt.ec_mul_loss_weight, opt.pair_mul_loss_weight
+    else:
+        a.w_mmd, a.w_emo, a.w_cau, a.w_pair = (opt.mmd_loss_weight, opt.emo_mul_loss_weight, opt.cau_mul_loss_weight,
+                                                opt.pair_mul_loss_weight)
     a.kl_weight, a.label_smoothing = kl_weight, opt.label_smoothing
     a.drop_p, a.drop_seed, a.drop_row_offset = drop
     a.mmd_alpha, a.mmd_eps = 0.1, 1e-5
     mode = getattr(opt, "disentangle", "mmd")
-    if mode not in ("mmd", "hsic", "none", "vi"):
-        raise L.CarelError("opt.disentangle must be 'mmd', 'hsic', 'vi' or 'none'")
-    a.dis_mode = {"mmd": 0, "hsic": 1, "none": 2, "vi": 2}[mode]      # vi: the CLUB term is added outside the tail (vi_upper)
+    if mode not in DISENTANGLE_MODES:
+        raise L.CarelError("opt.disentangle must be 'mmd', 'hsic', 'vi', 'gan' or 'none'")
+    # vi: the CLUB term is added outside the tail (vi_upper); gan: the adversaries run beside it (gan_disc)
+    a.dis_mode = {"mmd": 0, "hsic": 1, "none": 2, "vi": 2, "gan": 2}[mode]
     if mode == "hsic":
         a.w_mmd = getattr(opt, "hsic_loss_weight", 1.0)      # the HSIC script adds the statistic unweighted
     a.emo_bce = int(getattr(opt, "emotion_head", "ce") == "bce")
+    if mode == "gan" and not a.emo_bce:
+        raise L.CarelError("opt.disentangle == 'gan' needs opt.emotion_head == 'bce' (one-logit heads, drl_classifier_ec_gan.py:496-526)")
     a.global_label_sum = None if global_label_sum is None else global_label_sum.data_ptr()
     a.global_n, a.global_row_offset = global_n, global_row_offset
     a.z_global = None if z_global is None else z_global.data_ptr()
@@ -295,6 +304,43 @@ def vi_upper(z, net, perm):
     a.perm, a.loss_out, a.dz = perm.data_ptr(), loss.data_ptr(), dz.data_ptr()
     L.check(L.load().carel_vi_upper(C.byref(a), L.current_stream()), "carel_vi_upper")
     return loss, dz
+
+
+GAN_TERM_NAMES = ("ec_disc_loss", "ce_disc_loss", "ec_entropy", "ce_entropy")
+
+
+def gan_disc(z, emo_labels, cau_labels, disc_w, disc_b, opt, terms, g_loss_w, g_loss_b, g_ent_w, g_ent_b, *, drop=(0.0, 0, 0), vae_loss_in=None):
+    """carel_gan_disc: the two adversaries of drl_classifier_ec_gan.py on the sampled embeddings z f32 [B, 2*ec_dim].
+    disc_w / disc_b and the four g_* : pairs (ec_disc, ce_disc) of f32 device tensors ([ec_dim] weights, [1] biases); terms: f32 [8]
+    -> GAN_TERM_NAMES in [0..3] and, with vae_loss_in (f32 [1]), the vae loss plus the weighted entropies in [4]."""
+    ts = [z, emo_labels, cau_labels, terms, *disc_w, *disc_b, *g_loss_w, *g_loss_b, *g_ent_w, *g_ent_b]
+    _chk_cuda(*ts, vae_loss_in)
+    if any(t.dtype != torch.float32 for t in ts) or z.dim() != 2 or z.shape[1] % 2 or not z.is_contiguous():
+        raise L.CarelError("gan_disc: float32 tensors and a contiguous z [batch, 2*ec_dim] are required")
+    B, D = z.shape[0], z.shape[1] // 2
+    if emo_labels.numel() != B or cau_labels.numel() != B or not emo_labels.is_contiguous() or not cau_labels.is_contiguous():
+        raise L.CarelError("gan_disc: the emotion / cause labels are contiguous f32 [batch] tensors")
+    if terms.numel() < 8 or any(w.numel() != D for w in (*disc_w, *g_loss_w, *g_ent_w)) or any(b.numel() != 1 for b in (*disc_b, *g_loss_b, *g_ent_b)):
+        raise L.CarelError("gan_disc: terms holds 8 floats, weights and their images ec_dim, biases and their images 1")
+    a = L.GanArgs()
+    a.z, a.batch, a.ec_dim = z.data_ptr(), B, D
+    a.emo_labels, a.cau_labels = emo_labels.data_ptr(), cau_labels.data_ptr()
+    for i in range(2):
+        a.disc_w[i], a.disc_b[i] = disc_w[i].data_ptr(), disc_b[i].data_ptr()
+        a.g_loss_w[i], a.g_loss_b[i] = g_loss_w[i].data_ptr(), g_loss_b[i].data_ptr()
+        a.g_ent_w[i], a.g_ent_b[i] = g_ent_w[i].data_ptr(), g_ent_b[i].data_ptr()
+    a.label_smoothing, a.epsilon = opt.label_smoothing, opt.epsilon
+    a.drop_p, a.drop_seed, a.drop_row_offset = drop
+    a.vae_loss_in = None if vae_loss_in is None else vae_loss_in.data_ptr()
+    a.w_entropy = getattr(opt, "ecce_adv_loss_weight", 1.0)
+    a.terms = terms.data_ptr()
+    L.check(L.load().carel_gan_disc(C.byref(a), L.current_stream()), "carel_gan_disc")
+
+
+def axpy_(dst, src, scale_dev, accumulate):
+    """dst = (accumulate ? dst : 0) + *scale_dev * src (carel_axpy_f32; scale_dev: device f32 [1])."""
+    L.check(L.load().carel_axpy_f32(dst.data_ptr(), src.data_ptr(), dst.numel(), scale_dev.data_ptr(), int(accumulate), L.current_stream()),
+            "carel_axpy_f32")
 
 
 def bow_expand(trip, nnz, out):

@@ -2,7 +2,8 @@
 `load_ckp` (drl_classifier_ec_mmd_final_mul.py :603-628, :734-799, :802-922), same signatures and control
 flow; `opt` is an explicit keyword instead of a module global.  With two optimisers it runs the VI ablation's
 two-phase step (drl_classifier_ec_vi.py :723-790); with six, the adversarial step of drl_classifier_en.py (:904-947: five
-discriminator backward calls, the vae backward, six optimiser steps; evaluation on sigmoid(logits), :975-976).  The step body (:823-845) is unchanged: the
+discriminator backward calls, the vae backward, six optimiser steps; evaluation on sigmoid(logits), :975-976); with three, the adversarial
+step of the GAN ablation drl_classifier_ec_gan.py (:784-811: two discriminator backward calls, the vae backward, three steps).  The step body (:823-845) is unchanged: the
 model/optimiser objects it calls are carel_vae_amd.DrlClassifier and FusedAdam (or any torch optimiser).
 """
 import os
@@ -140,6 +141,7 @@ def train(train_loader, test_loader, model, optimizers, device, num_unpred_pairs
     opt = opt if opt is not None else model.opt
     vi = len(optimizers) == 2       # VI ablation (drl_classifier_ec_vi.py:723-725): [ec_aprx_opt, vae_and_cls_opt]
     en = len(optimizers) == 6       # drl_classifier_en.py:884: five discriminator optimisers + vae_and_cls_opt
+    gan = len(optimizers) == 3      # drl_classifier_ec_gan.py:762: [ec_disc_opt, ce_disc_opt, vae_and_cls_opt]
     ec_aprx_opt, vae_and_cls_opt = optimizers if vi else (None, optimizers[-1])
     max_p = max_r = max_f1 = 0.0
     self_p = self_r = self_f1 = 0.0
@@ -165,7 +167,7 @@ def train(train_loader, test_loader, model, optimizers, device, num_unpred_pairs
             att = batch["attention_masks"].to(device, dtype=torch.long, non_blocking=True)
             tt = batch["token_type_ids"].to(device, dtype=torch.long, non_blocking=True)
             labels = batch["labels"].to(device, dtype=torch.float, non_blocking=True)
-            emo = batch["emo_labels"].to(device, dtype=torch.float if en else torch.long, non_blocking=True)
+            emo = batch["emo_labels"].to(device, dtype=torch.float if (en or gan) else torch.long, non_blocking=True)
             cau = batch["cau_labels"].to(device, dtype=torch.float, non_blocking=True)
             bow = batch["bow_reps"].to(device, dtype=torch.float, non_blocking=True)
             if en:                  # drl_classifier_en.py:913-947
@@ -187,6 +189,19 @@ def train(train_loader, test_loader, model, optimizers, device, num_unpred_pairs
                 for o in optimizers:
                     o.step()
                 running.add(sum(l.detach() for l in losses), epoch, iteration)
+                continue
+            if gan:                 # drl_classifier_ec_gan.py:784-811
+                ec_disc_opt, ce_disc_opt, _ = optimizers
+                ec_disc_loss, ce_disc_loss, loss = model(ids, att, tt, emo, cau, labels, bow, iteration, **kw)
+                ec_disc_opt.zero_grad()
+                ec_disc_loss.backward(retain_graph=True)
+                ce_disc_opt.zero_grad()
+                ce_disc_loss.backward(retain_graph=True)
+                vae_and_cls_opt.zero_grad()
+                loss.backward()
+                for o in optimizers:
+                    o.step()
+                running.add(ec_disc_loss.detach() + ce_disc_loss.detach() + loss.detach(), epoch, iteration)
                 continue
             if vi:                  # two-phase step, drl_classifier_ec_vi.py:754-774
                 e_embedding, c_embedding, ec_aprx_loss, loss = model(ids, att, tt, emo, cau, labels, bow, iteration, **kw)

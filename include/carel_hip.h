@@ -693,6 +693,40 @@ int carel_vi_aprx(const carel_vi_args* args, void* stream);
 int carel_vi_upper(const carel_vi_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Adversarial (GAN) disentangler of the two-space ablation script drl_classifier_ec_gan.py: the two one-logit
+ * adversaries on the DETACHED sampled embeddings z = [e | c] f32 [B, 2*ec_dim] (:430-477)
+ *   disc 0 = ec_disc: p = sigmoid(w . dropout(c) + b), scored against the EMOTION labels   (:222-225)
+ *   disc 1 = ce_disc: p = sigmoid(w . dropout(e) + b), scored against the CAUSE labels     (:231-234)
+ *   loss    = mean_b BCELoss(p, y (1 - label_smoothing) + label_smoothing)   (logs clamped at -100, :458-470)
+ *   entropy = mean_b p log(p + epsilon)                                       (:472-477; p log p, not a binary entropy)
+ * ONE launch writes terms[0..3] = ec_disc_loss, ce_disc_loss, ec_entropy, ce_entropy and, for UNIT upstream gradients
+ * (the losses are roots of the graph; the caller scales), the four gradient images over [weight (ec_dim), bias]:
+ *   g_loss_w/b[i] = d loss_i / d disc_i,   g_ent_w/b[i] = d entropy_i / d disc_i.
+ * Because of the detach nothing here reaches z: there is no dz.  With vae_loss_in (f32 [1], the tail's terms[8]) also
+ * terms[4] = *vae_loss_in + w_entropy * (ec_entropy + ce_entropy), the vae_and_classifier_loss of :275-279.
+ * Dropout: the library's counter-based masks at sites 103 (ec_disc's input) and 104 (ce_disc's input), element index
+ * (drop_row_offset + b) * ec_dim + k.  Every sum runs in a fixed order (no atomics): the same inputs give the same bits.
+ * 1 <= batch <= 1024, 1 <= ec_dim <= 32 (the tail's limits).  Bad arguments return before any HIP call; nothing is
+ * allocated and the host is never synchronised.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct carel_gan_args {
+  const void* z;                     /* f32 [B, 2*ec_dim] (carel_tail_args.z) */
+  int32_t batch, ec_dim;
+  const void* emo_labels;            /* f32 [B] */
+  const void* cau_labels;            /* f32 [B] */
+  const void* disc_w[2];             /* f32 [ec_dim]: ec_disc.weight, ce_disc.weight */
+  const void* disc_b[2];             /* f32 [1] */
+  float label_smoothing, epsilon;
+  float drop_p; uint32_t drop_seed; uint32_t drop_row_offset;
+  const void* vae_loss_in;           /* f32 [1] or NULL */
+  float w_entropy;                   /* ecce_adv_loss_weight (used for terms[4] only) */
+  void* terms;                       /* f32 [8]: 0..3 as above, 4 = total (with vae_loss_in), 5..7 unused */
+  void* g_loss_w[2]; void* g_loss_b[2];
+  void* g_ent_w[2]; void* g_ent_b[2];
+} carel_gan_args;
+int carel_gan_disc(const carel_gan_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Tail of the three-space adversarial model of drl_classifier_en.py (config 4): replaces everything after
  * `pooler_output` in DrlClassifier.forward (drl_classifier_en.py:220-334) and the gradient side of the six
  * backward calls of its training step (:919-939).  fp32 throughout.
