@@ -60,13 +60,16 @@ int layernorm_fwd_slabs(const void* slabs, int splits, const void* bias, const v
 // half-batch chains): the split factor is then chosen as for ONE GEMM over all their rows -- same K partition, same bits; gemm.hip
 // (| GEMM_EX_FIXED_ROWS: M is the same whatever the batch -- the [CLS]-only last layer -- so a finer K partition is allowed)
 constexpr int GEMM_EX_FIXED_ROWS = 0x100;
-// (round 4) | GEMM_EX_DEFER_EPILOGUE: if this GEMM runs split-K into slabs, do NOT launch its slab epilogue: the caller's next kernel reads
+// (round 4) | GEMM_EX_DEFER_EPILOGUE: this GEMM runs split-K into slabs; do NOT launch its slab epilogue: the caller's next kernel reads
 // the slabs itself (LayerNorm fused behind the split GEMMs of packed ECPE batches: layernorm_bwd_rows_slabs / layernorm_fwd_slabs).  Only
-// together with a plan: gemm_bf16_split_plan() tells how many slabs the same call would write (1 = it does not split: do not defer).
+// for a call whose plan says so: gemm_bf16_split_plan() of the same arguments and flags returns the slabs it writes, and with 1 (single
+// pass) the flag is an argument error and nothing is launched.
 constexpr int GEMM_EX_DEFER_EPILOGUE = 0x200;
-constexpr int GEMM_EX_PLAN_ONLY = 0x400;       // (internal to gemm.hip)
+// Both validate the call, fill the kernel parameters and plan it with the one decision function of gemm.hip (gemm_plan: kernel family,
+// slabs, tile width, under every tuning-hook state); gemm_bf16_ex then launches exactly that plan, gemm_bf16_split_plan returns its slab
+// count (1 = single pass, also for a call that would be refused) and launches nothing.
 int gemm_bf16_ex(const carel_gemm_args* a, int split_tile_factor, void* stream);
-int gemm_bf16_split_plan(const carel_gemm_args* a, int split_tile_factor);       // slabs the internal split-K path would write for this call; 1 = single pass
+int gemm_bf16_split_plan(const carel_gemm_args* a, int split_tile_factor);
 // largest value carel_gemm_wgrad_splits(M, N, T) can take under any tuning-hook setting (slab buffer sizing); gemm.hip
 int gemm_wgrad_splits_max(int M, int N, long T);
 int embed_ln_bwd_ex(const carel_embed_args* a, const void* dx0, void* dword, void* dpos, void* dtype_, void* dgamma, void* dbeta,

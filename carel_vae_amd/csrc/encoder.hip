@@ -173,11 +173,15 @@ CAREL_TUNABLE(int, g_wgrad_group, 1);       // (experiments build: hook 240 / 24
 int wgrad_group_enabled() { return g_wgrad_group; }
 CAREL_TUNABLE(int, g_ln_resid, 1);          // tuning hook (carel_gemm_set_variant(230 / 231)): LayerNorm f32 outputs written and read back / recomputed by the next epilogue
 int ln_resid_enabled() { return g_ln_resid; }
-int gemm_call(const void* A, const void* B, long lda, long ldb, int M, int N, int K, int form, int epi, int splits, void* out_bf16,
-              void* out2, void* out_f32, const void* bias, const void* resid, const void* aux, uint32_t seed, uint32_t site,
-              uint32_t off, float p, void* stream, void* colsum_part = nullptr, const void* row_map = nullptr, void* ws = nullptr,
-              size_t ws_bytes = 0, int split_tile_factor = 1, const LnResid* lnres = nullptr, int* plan = nullptr) {
-  carel_gemm_args g;
+// One GEMM of the encoder: its operands, written once, and the flags word (chain count | GEMM_EX_*) that both its plan and its launch take
+struct GemmCall { carel_gemm_args g; int flags; };
+GemmCall gemm_fill(const void* A, const void* B, long lda, long ldb, int M, int N, int K, int form, int epi, int splits, void* out_bf16,
+                   void* out2, void* out_f32, const void* bias, const void* resid, const void* aux, uint32_t seed, uint32_t site,
+                   uint32_t off, float p, void* colsum_part = nullptr, const void* row_map = nullptr, void* ws = nullptr,
+                   size_t ws_bytes = 0, int split_tile_factor = 1, const LnResid* lnres = nullptr) {
+  GemmCall c;
+  c.flags = split_tile_factor;
+  carel_gemm_args& g = c.g;
   g.resid_ln_stats = lnres ? lnres->stats : nullptr; g.resid_ln_gamma = lnres ? lnres->gamma : nullptr; g.resid_ln_beta = lnres ? lnres->beta : nullptr;
   g.A = A; g.B = B; g.lda = lda; g.ldb = ldb; g.ldc = N; g.M = M; g.N = N; g.K = K; g.form = form; g.epilogue = epi; g.splits = splits;
   g.out_bf16 = out_bf16; g.out2_bf16 = out2; g.out_f32 = out_f32; g.bias = bias; g.resid_f32 = resid; g.aux_bf16 = aux;
@@ -187,9 +191,15 @@ int gemm_call(const void* A, const void* B, long lda, long ldb, int M, int N, in
   // written by nobody else: pair split-K may keep its flags there.  Not for the second forward chain, whose workspace is the
   // weight-gradient slab area.
   g.splitk_ws_zeroed = (ws != nullptr && (split_tile_factor & 0xff) == 1) ? 1 : 0;
-  if (plan) { *plan = gemm_bf16_split_plan(&g, split_tile_factor); return CAREL_OK; }      // no launch: how many slabs would this call write?
-  return gemm_bf16_ex(&g, split_tile_factor, stream);
+  return c;
 }
+// A GEMM whose only reader is the LayerNorm kernel behind it.  fuse: where the plan splits it into fp32 slabs, its slab epilogue is left to that
+// kernel (GEMM_EX_DEFER_EPILOGUE).  *slabs: how many slabs that kernel must sum; 1 = the GEMM wrote its output itself.
+int gemm_run_ln(const GemmCall& c, bool fuse, void* stream, int* slabs) {
+  *slabs = fuse ? gemm_bf16_split_plan(&c.g, c.flags) : 1;
+  return gemm_bf16_ex(&c.g, c.flags | (*slabs > 1 ? GEMM_EX_DEFER_EPILOGUE : 0), stream);
+}
+int gemm_run(const GemmCall& c, void* stream) { return gemm_bf16_ex(&c.g, c.flags, stream); }
 
 // dW[M,N] = A^T[M x T] * B[T x N]  (A = dY [T,M], B = X [T,N])  via split-K slabs.  With db != null the bias gradient
 // db[M] = column sums of dY comes out of the same GEMM (ones-vector MFMA) as [splits][M] partials behind the slabs.
@@ -199,12 +209,8 @@ struct LnPartials { const void* partials; long rows; void* dgamma; void* dbeta; 
 int wgrad_call(const void* dY, const void* X, long T, int M, int N, void* slabs, void* dW, void* stream, void* db = nullptr,
                const LnPartials* lnp = nullptr) {
   const int splits = wgrad_splits(T, M, N);
-  carel_gemm_args g;
-  g.A = dY; g.B = X; g.lda = M; g.ldb = N; g.ldc = N; g.M = M; g.N = N; g.K = (int)T; g.form = CAREL_GEMM_TN; g.epilogue = CAREL_EPI_SLAB_F32;
-  g.splits = splits; g.out_bf16 = nullptr; g.out2_bf16 = nullptr; g.out_f32 = slabs; g.bias = nullptr; g.resid_f32 = nullptr; g.aux_bf16 = nullptr;
-  g.drop_seed = 0; g.drop_site = 0; g.drop_idx_offset = 0; g.drop_p = 0.f; g.drop_row_map = nullptr; g.colsum_part = nullptr;
-  g.splitk_ws = nullptr; g.splitk_ws_bytes = 0; g.splitk_ws_zeroed = 0;
-  g.resid_ln_stats = nullptr; g.resid_ln_gamma = nullptr; g.resid_ln_beta = nullptr;
+  carel_gemm_args g = gemm_fill(dY, X, M, N, M, N, (int)T, CAREL_GEMM_TN, CAREL_EPI_SLAB_F32, splits, nullptr, nullptr, slabs, nullptr, nullptr, nullptr, 0, 0, 0,
+                                0.f).g;
   float* cs = db ? (float*)slabs + (size_t)splits * M * N : nullptr;
   g.colsum_a = cs;
   if (splits == 1) {                 // one slab IS the result: write it (and the bias sums) in place, nothing to reduce
@@ -283,8 +289,8 @@ static int forward_layers(const carel_encoder_args* a, int l0, int l1, long b0, 
     la.xin_bf16 += (size_t)r0 * EH * 2; la.qkv += (size_t)r0 * 3 * EH * 2; la.lse += (size_t)b0 * ENH * S * 4; la.ctx += (size_t)r0 * EH * 2;
     la.h1 += (size_t)r0 * EH * 4; la.st1 += (size_t)r0 * 2 * 4; la.x1_bf16 += (size_t)r0 * EH * 2; la.u += (size_t)r0 * EI * 2;
     la.g += (size_t)r0 * EI * 2; la.h2 += (size_t)r0 * EH * 4; la.st2 += (size_t)r0 * 2 * 4;
-    if ((rc = gemm_call(la.xin_bf16, w.qkv_w, EH, EH, (int)T, 3 * EH, EH, CAREL_GEMM_NT, CAREL_EPI_BIAS_BF16, 1, la.qkv, nullptr, nullptr,
-                        w.qkv_b, nullptr, nullptr, 0, 0, 0, 0.f, stream, nullptr, nullptr, ws, ws_bytes, chains))) return rc;
+    if ((rc = gemm_run(gemm_fill(la.xin_bf16, w.qkv_w, EH, EH, (int)T, 3 * EH, EH, CAREL_GEMM_NT, CAREL_EPI_BIAS_BF16, 1, la.qkv, nullptr, nullptr,
+                                 w.qkv_b, nullptr, nullptr, 0, 0, 0, 0.f, nullptr, nullptr, ws, ws_bytes, chains), stream))) return rc;
     carel_attn_args at;
     at.qkv = la.qkv; at.attention_mask = a->attention_mask ? (const void*)((const long*)a->attention_mask + b0 * S) : nullptr;
     at.ctx = la.ctx; at.lse = la.lse; at.dctx = nullptr; at.dqkv = nullptr;
@@ -340,45 +346,32 @@ static int forward_layers(const carel_encoder_args* a, int l0, int l1, long b0, 
       return carel_gemm_rowln(&ra, stream);
 #endif
     };
+    // the two-kernel path: the linear, then the LayerNorm.  (packed batches: where the linear runs split-K into slabs, its slab epilogue -- bias, dropout,
+    // residual -- is the first half of the LayerNorm kernel behind it: one launch and one round trip of the rows fewer per sub-layer;
+    // ln_fwd_slabs_kernel, same expressions in the same order)
+    auto linear_then_ln = [&](const void* A, const void* W, int K, const void* bias, const void* resid, const LnResid* lr, int site, const void* g,
+                              const void* bt, void* h, void* xf, void* xbf, void* st) -> int {
+      int slabs;
+      if ((rc = gemm_run_ln(gemm_fill(A, W, K, K, (int)R, EH, K, CAREL_GEMM_NT, CAREL_EPI_BIAS_DROP_RESID, 1, nullptr, nullptr, h, bias, resid, nullptr, a->drop_seed,
+                                      site, hoff, a->hidden_dropout, nullptr, rmap, ws, ws_bytes, chains | fixed, lr),
+                            ln_slab_fusion_enabled() && ws, stream, &slabs))) return rc;
+      if (slabs > 1)
+        return layernorm_fwd_slabs(ws, slabs, bias, resid, lr ? lr->stats : nullptr, lr ? lr->gamma : nullptr, lr ? lr->beta : nullptr, a->drop_seed, site, hoff,
+                                   a->hidden_dropout, rmap, h, g, bt, a->ln_eps, R, xf, xbf, st, (hipStream_t)stream);
+      return carel_layernorm_fwd(h, g, bt, a->ln_eps, R, EH, xf, xbf, st, stream);
+    };
     if (fuse_ln) {
       if ((rc = linear_ln(Actx, w.out_w, EH, w.out_b, res1, 2 + 3 * i, w.ln1_g, w.ln1_b, a->inference ? nullptr : la.h1, xb, la.x1_bf16, la.st1))) return rc;
-    } else {
-    // (packed batches: where the linear runs split-K into slabs, its slab epilogue -- bias, dropout, residual -- is the first half of the LayerNorm
-    // kernel behind it: one launch and one round trip of the rows fewer per sub-layer; ln_fwd_slabs_kernel, same expressions in the same order)
-    int out_slabs = 1;
-    if (ln_slab_fusion_enabled() && ws &&
-        (rc = gemm_call(Actx, w.out_w, EH, EH, (int)R, EH, EH, CAREL_GEMM_NT, CAREL_EPI_BIAS_DROP_RESID, 1, nullptr, nullptr, la.h1, w.out_b, res1, nullptr,
-                        a->drop_seed, 2 + 3 * i, hoff, a->hidden_dropout, stream, nullptr, rmap, ws, ws_bytes, chains | fixed, plr1, &out_slabs))) return rc;
-    if ((rc = gemm_call(Actx, w.out_w, EH, EH, (int)R, EH, EH, CAREL_GEMM_NT, CAREL_EPI_BIAS_DROP_RESID, 1, nullptr, nullptr, la.h1,
-                        w.out_b, res1, nullptr, a->drop_seed, 2 + 3 * i, hoff, a->hidden_dropout, stream, nullptr, rmap, ws, ws_bytes,
-                        chains | fixed | (out_slabs > 1 ? GEMM_EX_DEFER_EPILOGUE : 0), plr1))) return rc;
-    if (out_slabs > 1) {
-      if ((rc = layernorm_fwd_slabs(ws, out_slabs, w.out_b, res1, plr1 ? plr1->stats : nullptr, plr1 ? plr1->gamma : nullptr, plr1 ? plr1->beta : nullptr,
-                                    a->drop_seed, 2 + 3 * i, hoff, a->hidden_dropout, rmap, la.h1, w.ln1_g, w.ln1_b, a->ln_eps, R, lnres2 ? nullptr : xb,
-                                    la.x1_bf16, la.st1, (hipStream_t)stream))) return rc;
-    } else if ((rc = carel_layernorm_fwd(la.h1, w.ln1_g, w.ln1_b, a->ln_eps, R, EH, lnres2 ? nullptr : xb, la.x1_bf16, la.st1, stream))) return rc;
-    }
-    if ((rc = gemm_call(la.x1_bf16, w.ffn1_w, EH, EH, (int)R, EI, EH, CAREL_GEMM_NT, a->inference ? CAREL_EPI_BIAS_GELU : CAREL_EPI_BIAS_GELU_DG, 1, a->inference ? nullptr : la.u, la.g, nullptr,
-                        w.ffn1_b, nullptr, nullptr, 0, 0, 0, 0.f, stream, nullptr, nullptr, ws, ws_bytes, chains | fixed))) return rc;
+    } else if ((rc = linear_then_ln(Actx, w.out_w, EH, w.out_b, res1, plr1, 2 + 3 * i, w.ln1_g, w.ln1_b, la.h1, lnres2 ? nullptr : xb, la.x1_bf16, la.st1))) return rc;
+    if ((rc = gemm_run(gemm_fill(la.x1_bf16, w.ffn1_w, EH, EH, (int)R, EI, EH, CAREL_GEMM_NT, a->inference ? CAREL_EPI_BIAS_GELU : CAREL_EPI_BIAS_GELU_DG, 1,
+                                 a->inference ? nullptr : la.u, la.g, nullptr, w.ffn1_b, nullptr, nullptr, 0, 0, 0, 0.f, nullptr, nullptr, ws, ws_bytes, chains | fixed),
+                       stream))) return rc;
     char* next_bf16 = nullptr;
     if (i + 1 < a->n_layers) next_bf16 = layer_act(l, base, i + 1, a->inference).xin_bf16 + (size_t)r0 * EH * 2;
     if (fuse_ln && gemm_rowln_wanted_k(EI)) {
       if ((rc = linear_ln(la.g, w.ffn2_w, EI, w.ffn2_b, xb, 3 + 3 * i, w.ln2_g, w.ln2_b, a->inference ? nullptr : la.h2, xa, next_bf16, la.st2))) return rc;
-    } else {
-    const void* res2 = lnres2 ? (const void*)la.h1 : (const void*)xb;
-    int ffn2_slabs = 1;
-    if (ln_slab_fusion_enabled() && ws &&
-        (rc = gemm_call(la.g, w.ffn2_w, EI, EI, (int)R, EH, EI, CAREL_GEMM_NT, CAREL_EPI_BIAS_DROP_RESID, 1, nullptr, nullptr, la.h2, w.ffn2_b, res2, nullptr,
-                        a->drop_seed, 3 + 3 * i, hoff, a->hidden_dropout, stream, nullptr, rmap, ws, ws_bytes, chains | fixed, lnres2 ? &lr2 : nullptr, &ffn2_slabs))) return rc;
-    if ((rc = gemm_call(la.g, w.ffn2_w, EI, EI, (int)R, EH, EI, CAREL_GEMM_NT, CAREL_EPI_BIAS_DROP_RESID, 1, nullptr, nullptr, la.h2,
-                        w.ffn2_b, res2, nullptr, a->drop_seed, 3 + 3 * i, hoff, a->hidden_dropout, stream, nullptr, rmap, ws,
-                        ws_bytes, chains | fixed | (ffn2_slabs > 1 ? GEMM_EX_DEFER_EPILOGUE : 0), lnres2 ? &lr2 : nullptr))) return rc;
-    if (ffn2_slabs > 1) {
-      if ((rc = layernorm_fwd_slabs(ws, ffn2_slabs, w.ffn2_b, res2, lnres2 ? lr2.stats : nullptr, lnres2 ? lr2.gamma : nullptr, lnres2 ? lr2.beta : nullptr,
-                                    a->drop_seed, 3 + 3 * i, hoff, a->hidden_dropout, rmap, la.h2, w.ln2_g, w.ln2_b, a->ln_eps, R, need_xa ? xa : nullptr,
-                                    next_bf16, la.st2, (hipStream_t)stream))) return rc;
-    } else if ((rc = carel_layernorm_fwd(la.h2, w.ln2_g, w.ln2_b, a->ln_eps, R, EH, need_xa ? xa : nullptr, next_bf16, la.st2, stream))) return rc;
-    }
+    } else if ((rc = linear_then_ln(la.g, w.ffn2_w, EI, w.ffn2_b, lnres2 ? (const void*)la.h1 : (const void*)xb, lnres2 ? &lr2 : nullptr, 3 + 3 * i, w.ln2_g,
+                                    w.ln2_b, la.h2, need_xa ? xa : nullptr, next_bf16, la.st2))) return rc;
   }
   return CAREL_OK;
 }
@@ -540,11 +533,10 @@ extern "C" int carel_encoder_backward_layer(const carel_encoder_args* a, int32_t
   // layer below, i.e. the NEXT call), the epilogue is deferred into that kernel (GEMM_EX_DEFER_EPILOGUE, layernorm_bwd_rows_slabs): same bits,
   // one launch and one round trip of the rows fewer per sub-layer.  The decision is a function of the shapes only, so this call knows what
   // the previous one did.  Layer 0's QKV data gradient feeds the embedding backward and is never deferred.
-  int qkv_slabs = 1;
-  if (ln_slab_fusion_enabled()) {
-    if ((rc = gemm_call(s.dqkv, w.qkv_w, 3 * EH, EH, (int)T, EH, 3 * EH, CAREL_GEMM_NN, CAREL_EPI_ADD_F32, 1, nullptr, nullptr, a->dx, nullptr,
-                        s.dy, nullptr, 0, 0, 0, 0.f, stream, nullptr, nullptr, s.ws, ws_bytes, 1, nullptr, &qkv_slabs))) return rc;
-  }
+  // (the QKV data gradient: filled here, launched at the bottom of this call from the same struct; its residual dh1, no input of the plan, is set there)
+  GemmCall gqkv = gemm_fill(s.dqkv, w.qkv_w, 3 * EH, EH, (int)T, EH, 3 * EH, CAREL_GEMM_NN, CAREL_EPI_ADD_F32, 1, nullptr, nullptr, a->dx, nullptr, s.dy,
+                            nullptr, 0, 0, 0, 0.f, nullptr, nullptr, s.ws, ws_bytes, 1);
+  const int qkv_slabs = ln_slab_fusion_enabled() ? gemm_bf16_split_plan(&gqkv.g, gqkv.flags) : 1;
   // (did the call for layer + 1 defer its QKV epilogue?  then dx = sum of the slabs + s.dy; a [CLS]-only last layer never defers)
   const bool dx_in_slabs = qkv_slabs > 1 && layer + 1 < a->n_layers && !(a->n_cls > 0 && layer + 2 == a->n_layers);
   // LN2 backward: dx -> dh2 (s.dy), dyb (dropout-masked, bf16), dgamma/dbeta, FFN2 bias grad
@@ -563,8 +555,8 @@ extern "C" int carel_encoder_backward_layer(const carel_encoder_args* a, int32_t
     if ((rc = group_done(0))) return rc;
   }
   if ((rc = wait_group(1))) return rc;
-  if ((rc = gemm_call(s.dyb, w.ffn2_w, EH, EI, (int)R, EI, EH, CAREL_GEMM_NN, CAREL_EPI_MUL_BF16, 1, s.du, nullptr, nullptr, nullptr,
-                      nullptr, la.u, 0, 0, 0, 0.f, stream, nullptr))) return rc;
+  if ((rc = gemm_run(gemm_fill(s.dyb, w.ffn2_w, EH, EI, (int)R, EI, EH, CAREL_GEMM_NN, CAREL_EPI_MUL_BF16, 1, s.du, nullptr, nullptr, nullptr,
+                               nullptr, la.u, 0, 0, 0, 0.f, nullptr), stream))) return rc;
   // FFN1: dx1 = du W1 + dh2 -> a->dx ; dW1 = du^T x1, and the FFN1 bias gradient (column sums of du) from the same GEMM: its ones-vector
   // MFMAs are free there (43.2 vs 43.1 us, tools/bench_wgrad_colsum.py), the fused column sums of the data-gradient epilogue cost 3.9 us
   if (!grouped) {
@@ -572,14 +564,10 @@ extern "C" int carel_encoder_backward_layer(const carel_encoder_args* a, int32_t
     if ((rc = wgrad_call(s.du, la.x1_bf16, R, EI, EH, s.slabs, g.ffn1_w, wstream, g.ffn1_b))) return rc;
     if ((rc = group_done(1))) return rc;
   }
-  int ffn1_slabs = 1;
-  if (ln_slab_fusion_enabled() && !cls_only) {
-    if ((rc = gemm_call(s.du, w.ffn1_w, EI, EH, (int)R, EH, EI, CAREL_GEMM_NN, CAREL_EPI_ADD_F32, 1, nullptr, nullptr, a->dx, nullptr, s.dy,
-                        nullptr, 0, 0, 0, 0.f, stream, nullptr, nullptr, s.ws, ws_bytes, 1, nullptr, &ffn1_slabs))) return rc;
-  }
-  if ((rc = gemm_call(s.du, w.ffn1_w, EI, EH, (int)R, EH, EI, CAREL_GEMM_NN, CAREL_EPI_ADD_F32, 1, nullptr, nullptr, a->dx, nullptr, s.dy,
-                      nullptr, 0, 0, 0, 0.f, stream, nullptr, nullptr, s.ws, ws_bytes,
-                      1 | (cls_only ? GEMM_EX_FIXED_ROWS : 0) | (ffn1_slabs > 1 ? GEMM_EX_DEFER_EPILOGUE : 0)))) return rc;
+  int ffn1_slabs;
+  if ((rc = gemm_run_ln(gemm_fill(s.du, w.ffn1_w, EI, EH, (int)R, EH, EI, CAREL_GEMM_NN, CAREL_EPI_ADD_F32, 1, nullptr, nullptr, a->dx, nullptr, s.dy, nullptr,
+                                  0, 0, 0, 0.f, nullptr, nullptr, s.ws, ws_bytes, 1 | (cls_only ? GEMM_EX_FIXED_ROWS : 0)),
+                        ln_slab_fusion_enabled() && !cls_only, stream, &ffn1_slabs))) return rc;
   // LN1 backward (its bf16 output goes to a second buffer: the FFN2 weight gradient may still be reading dyb)
   if ((rc = wait_group(2))) return rc;
   if (ffn1_slabs > 1) {          // dx = sum of the FFN1 data gradient's slabs + dh2 (s.dy), never stored
@@ -596,8 +584,8 @@ extern "C" int carel_encoder_backward_layer(const carel_encoder_args* a, int32_t
     if ((rc = group_done(2))) return rc;
   }
   if (cls_only && (rc = wait_group(3))) return rc;             // the compact result parks in dqkv
-  if ((rc = gemm_call(s.dyb2, w.out_w, EH, EH, (int)R, EH, EH, CAREL_GEMM_NN, CAREL_EPI_BIAS_BF16, 1, dctx_rows, nullptr, nullptr, nullptr,
-                      nullptr, nullptr, 0, 0, 0, 0.f, stream, nullptr, nullptr, s.ws, ws_bytes, 1 | (cls_only ? GEMM_EX_FIXED_ROWS : 0)))) return rc;
+  if ((rc = gemm_run(gemm_fill(s.dyb2, w.out_w, EH, EH, (int)R, EH, EH, CAREL_GEMM_NN, CAREL_EPI_BIAS_BF16, 1, dctx_rows, nullptr, nullptr, nullptr,
+                               nullptr, nullptr, 0, 0, 0, 0.f, nullptr, nullptr, s.ws, ws_bytes, 1 | (cls_only ? GEMM_EX_FIXED_ROWS : 0)), stream))) return rc;
   if (cls_only) {
     // expand the compact [CLS] gradients to token rows: dctx (attention backward input) and the residual-path
     // gradient dh1 (added by the QKV dgrad epilogue) are zero everywhere else
@@ -632,8 +620,8 @@ extern "C" int carel_encoder_backward_layer(const carel_encoder_args* a, int32_t
   else if ((rc = wgrad_call(s.dqkv, la.xin_bf16, T, 3 * EH, EH, s.slabs, g.qkv_w, wstream, g.qkv_b))) return rc;
   // (deferred: the next call's LayerNorm-2 backward adds the slabs and dh1 itself -- dh1 must then be s.dy, i.e. not the [CLS]-only layer's scattered rows)
   const bool defer_qkv = qkv_slabs > 1 && layer > 0 && !cls_only;
-  if ((rc = gemm_call(s.dqkv, w.qkv_w, 3 * EH, EH, (int)T, EH, 3 * EH, CAREL_GEMM_NN, CAREL_EPI_ADD_F32, 1, nullptr, nullptr, a->dx, nullptr,
-                      dh1_full, nullptr, 0, 0, 0, 0.f, stream, nullptr, nullptr, s.ws, ws_bytes, 1 | (defer_qkv ? GEMM_EX_DEFER_EPILOGUE : 0)))) return rc;
+  gqkv.g.resid_f32 = dh1_full;
+  if ((rc = gemm_bf16_ex(&gqkv.g, gqkv.flags | (defer_qkv ? GEMM_EX_DEFER_EPILOGUE : 0), stream))) return rc;
   if (!grouped && (rc = group_done(3))) return rc;
   if (sd) {
     // side stream: this layer's weight gradients are enqueued; main stream: those of the PREVIOUS call (layer + 1) are complete from here

@@ -496,124 +496,159 @@ static int split_pp_npn(const GemmParams& p, bool at, int sp) {
   return 0;
 }
 
-// result of the last GEMM_EX_PLAN_ONLY pass (gemm_bf16_split_plan): slabs, kernel family (CAREL_PLAN_*, include/carel_hip_experiments.h), npn
-static thread_local int tl_split_plan = 1, tl_plan_family = 0, tl_plan_npn = 0;
-enum { PLAN_PP = 1, PLAN_128 = 2, PLAN_BIG = 3, PLAN_PP_SLABS = 4, PLAN_128_SLABS = 5, PLAN_SM = 6 };
+// ---- the plan: which kernel runs a GEMM, and into how many fp32 slabs it splits along K ------------------------------------------------
+// Every shape predicate, heuristic and tuning hook that bears on the choice is read HERE and nowhere else: launch() executes the plan it is
+// given, gemm_bf16_split_plan / carel_gemm_split_plan hand it to callers that must know it in advance (GEMM_EX_DEFER_EPILOGUE).
+enum { PLAN_NONE = 0, PLAN_PP = 1, PLAN_128 = 2, PLAN_BIG = 3, PLAN_PP_SLABS = 4, PLAN_128_SLABS = 5, PLAN_SM = 6, PLAN_PAIR = 7, PLAN_TRI = 8 };
 #ifdef CAREL_EXPERIMENTS
 static_assert(PLAN_PP == CAREL_PLAN_PP && PLAN_128 == CAREL_PLAN_128 && PLAN_BIG == CAREL_PLAN_BIG && PLAN_PP_SLABS == CAREL_PLAN_PP_SLABS &&
-              PLAN_128_SLABS == CAREL_PLAN_128_SLABS && PLAN_SM == CAREL_PLAN_SM && CAREL_PLAN_FIXED_ROWS == GEMM_EX_FIXED_ROWS, "plan codes");
+              PLAN_128_SLABS == CAREL_PLAN_128_SLABS && PLAN_SM == CAREL_PLAN_SM && PLAN_PAIR == CAREL_PLAN_PAIR && PLAN_TRI == CAREL_PLAN_TRI &&
+              CAREL_PLAN_FIXED_ROWS == GEMM_EX_FIXED_ROWS, "plan codes");
 #endif
-template <bool AT, bool BT, int EPI>
-static int launch(const GemmParams& p, int splits, hipStream_t s) {
-  const bool plan_only = (p.split_tile_factor & GEMM_EX_PLAN_ONLY) != 0, defer = (p.split_tile_factor & GEMM_EX_DEFER_EPILOGUE) != 0;
-  if (plan_only) {          // the decisions below without a launch: which kernel, does this call take the internal split-K path, with how many slabs?
-    tl_split_plan = 1; tl_plan_family = 0; tl_plan_npn = 0;
-    if (const int sms = sm_plan(p, EPI, AT)) { tl_split_plan = sms; tl_plan_family = PLAN_SM; return CAREL_OK; }
-    const bool big_ok = (p.M % 256 == 0) && (p.N % 192 == 0), v1_ok = (p.M % 128 == 0) && (p.N % 128 == 0);
-    int rs = 1;
-    if (!AT && g_gemm_variant == 0) {
-      const bool only_pp = !((p.M % 128 == 0 && p.N % 128 == 0) || (p.M % 256 == 0 && p.N % 192 == 0));
-      rs = resid_split(p, EPI);
-      if (rs <= 1) {
-        if (const int npn = gemm_pp_pick(p, BT, EPI, only_pp ? 1 : -(p.K <= 768 ? g_pp_min_tiles_k768 : g_pp_min_tiles))) {
-          tl_plan_family = PLAN_PP; tl_plan_npn = npn;
-          return CAREL_OK;
-        }
-      }
-    } else if (!AT) {
-      return CAREL_OK;      // (tuning hooks: not planned)
-    }
-    if (big_ok && (!v1_ok || (g_gemm_variant == 0 && big_auto(p, splits)))) { tl_plan_family = PLAN_BIG; return CAREL_OK; }
-    if (!v1_ok) return CAREL_OK;
-    const int sp = (EPI != EPI_SLAB_F32 && p.splitk_ws) ? (rs > 1 ? rs : auto_splits(p, p.splitk_ws_bytes)) : 1;
-    if (sp > 1) {
-      tl_split_plan = sp; tl_plan_npn = split_pp_npn(p, AT, sp);
-      tl_plan_family = tl_plan_npn ? PLAN_PP_SLABS : PLAN_128_SLABS;
-    } else {
-      tl_plan_family = PLAN_128;
-    }
-    return CAREL_OK;
-  }
-#ifdef CAREL_EXPERIMENTS
-  if (const int sms = sm_plan(p, EPI, AT)) {
-    if (sms == 1) {
-      if (defer) return set_error(CAREL_ERR_ARG, "carel_gemm_bf16: internal: epilogue deferred for a GEMM that does not split (plan / launch disagree)");
-      return gemm_sm_launch(p, BT, EPI, 1, s);
-    }
-    GemmParams q = p;
-    q.K = p.K / sms; q.outf = p.splitk_ws; q.ldc = p.N; q.colsum_part = nullptr;
-    const int rc = gemm_sm_launch(q, BT, EPI_SLAB_F32, sms, s);
-    if (rc || defer) return rc;
-    const long chunks = (long)p.M * (p.N >> 3);
-    hipLaunchKernelGGL((slab_epilogue_kernel<EPI>), dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s, p, (const float*)p.splitk_ws, sms);
-    return check_launch("gemm_sm_kernel split-K + slab_epilogue_kernel");
-  }
-#endif
-  if (!AT && g_gemm_variant != 1 && g_gemm_variant != 2 && !(g_gemm_variant >= 11 && g_gemm_variant <= 19)) {
-    // row-major-A forms: the 256 x 96n ping-pong kernel (gemm_pp.hip) when the grid fills the chip (variant 3: always)
-#ifdef CAREL_EXPERIMENTS
-    if (p.pair_flags && p.ldc == p.N && !p.colsum_part && g_gemm_variant == 0 && gemm_pp_pick_pair(p, BT, EPI)) return gemm_pp_launch_pair(p, BT, EPI, s);
-#endif
-    // (a shape only the ping-pong kernel takes -- M not a multiple of 128 -- runs on it whatever the tile-count threshold says:
-    // gemm_shape_ok accepted it on that kernel's account)
-#ifdef CAREL_EXPERIMENTS
-    if (!BT && g_gemm_variant == 0 && p.ldc == p.N && gemm_tri_pick(p, EPI)) return gemm_tri_launch(p, EPI, s);
-#endif
-    const bool only_pp = !((p.M % 128 == 0 && p.N % 128 == 0) || (p.M % 256 == 0 && p.N % 192 == 0));
-    const int npn = (g_gemm_variant == 0 && resid_split(p, EPI) > 1) ? 0 :
-                    gemm_pp_pick(p, BT, EPI, (g_gemm_variant == 3 || g_gemm_variant >= 60 || only_pp) ? 1 : -(p.K <= 768 ? g_pp_min_tiles_k768 : g_pp_min_tiles));
+struct GemmPlan {
+  int family;     // PLAN_*; PLAN_NONE: no kernel takes this shape
+  int slabs;      // fp32 slabs of the internal split-K path (1 = single pass)
+  int npn;        // ping-pong kernel: tile width in units of 96 columns; else 0
+  int dbg;        // CAREL_GEMM_ABLATE builds: the timing ablation (wrong results) of that family's kernel; else 0
+};
+// (p.K = the contraction length of one of the caller's `splits` slices, K = the whole of it)
+static GemmPlan gemm_plan(const GemmParams& p, int form, int epi, int splits, int K) {
+  const bool at = form == CAREL_GEMM_TN, bt = form != CAREL_GEMM_NT;
+  const int v = g_gemm_variant;
+  const bool big_ok = (p.M % 256 == 0) && (p.N % 192 == 0), v1_ok = (p.M % 128 == 0) && (p.N % 128 == 0);
+  int rs = 1;
+  if (at) {
+    if (v != 1 && v != 2) {      // ping-pong kernel: K tiles dealt to the slices as evenly as possible
+      GemmParams q = p;
+      q.K = K;
+      const int npn = gemm_pp_pick_tn(q, splits);
+      const long wgs = npn ? (long)(q.M / 256) * (q.N / (96 * npn)) * splits : 0;
 #ifdef CAREL_GEMM_ABLATE
-    if (npn && !BT && EPI == EPI_BIAS_BF16 && g_gemm_variant >= 61 && g_gemm_variant <= 69) return gemm_pp_launch_dbg(p, npn, g_gemm_variant - 60, s);
+      if (npn == 2 && v >= 61 && v <= 68) return {PLAN_PP, 1, npn, v - 60};
 #endif
-    if (npn) return gemm_pp_launch(p, BT, EPI, npn, s);
+      // (the same floor as gemm_pp_wgrad_splits: whatever carel_gemm_wgrad_splits proposes for this kernel must be taken by it)
+      if (npn && (v == 3 || wgs >= 64)) return {PLAN_PP, 1, npn, 0};
+    }
+    if (K % (64 * splits)) return {PLAN_NONE, 1, 0, 0};       // (the tiles below want equal slices)
+  } else {
+    if (const int sms = sm_plan(p, epi, at)) return {PLAN_SM, sms, 0, 0};
+    if (v == 0) rs = resid_split(p, epi);
+    if (v != 1 && v != 2 && !(v >= 11 && v <= 19)) {
+      // row-major-A forms: the 256 x 96n ping-pong kernel (gemm_pp.hip) when the grid fills the chip (variant 3: always)
+#ifdef CAREL_EXPERIMENTS
+      if (p.pair_flags && p.ldc == p.N && !p.colsum_part && v == 0 && gemm_pp_pick_pair(p, bt, epi)) return {PLAN_PAIR, 1, 0, 0};
+      if (!bt && v == 0 && p.ldc == p.N && gemm_tri_pick(p, epi)) return {PLAN_TRI, 1, 0, 0};
+#endif
+      // (a shape only the ping-pong kernel takes -- M not a multiple of 128 -- runs on it whatever the tile-count threshold says:
+      // gemm_shape_ok accepted it on that kernel's account)
+      const bool force = v == 3 || v >= 60 || !(v1_ok || big_ok);
+      const int npn = rs > 1 ? 0 : gemm_pp_pick(p, bt, epi, force ? 1 : -(p.K <= 768 ? g_pp_min_tiles_k768 : g_pp_min_tiles));
+      if (npn) {
+#ifdef CAREL_GEMM_ABLATE
+        if (!bt && epi == EPI_BIAS_BF16 && v >= 61 && v <= 69) return {PLAN_PP, 1, npn, v - 60};
+#endif
+        return {PLAN_PP, 1, npn, 0};
+      }
+    }
   }
-  const bool big_ok = (p.M % 256 == 0) && (p.N % 192 == 0);
-  const bool v1_ok = (p.M % 128 == 0) && (p.N % 128 == 0);
   // big tile when asked for (variant 2) or, automatically, where it wins: wide outputs / weight gradients with enough
   // tiles to fill the chip (heuristic from tools/bench_gemm.py)
-  bool use_big = big_ok && (g_gemm_variant == 2 || (g_gemm_variant == 0 && (!v1_ok || big_auto(p, splits))));
-  if (use_big) return launch_big<AT, BT, EPI>(p, splits, s);
-  if (!v1_ok) return set_error(CAREL_ERR_SHAPE, "carel_gemm_bf16: shape fits neither tile (M=%d N=%d)", p.M, p.N);
-  dim3 grid(p.tiles_m * p.tiles_n, 1, splits);
+  if (big_ok && (v == 2 || (v == 0 && (!v1_ok || big_auto(p, splits))))) return {PLAN_BIG, 1, 0, 0};
+  if (!v1_ok) return {PLAN_NONE, 1, 0, 0};
 #ifdef CAREL_GEMM_ABLATE     // timing ablations (wrong results) are not part of the product library: build with -DCAREL_GEMM_ABLATE
-  if (!AT && !BT && EPI == EPI_BIAS_BF16 && g_gemm_variant >= 11 && g_gemm_variant <= 19) {
-    if (g_gemm_variant == 11) hipLaunchKernelGGL((gemm_kernel<false, false, EPI_BIAS_BF16, 1>), grid, dim3(256), 0, s, p);
-    if (g_gemm_variant == 12) hipLaunchKernelGGL((gemm_kernel<false, false, EPI_BIAS_BF16, 2>), grid, dim3(256), 0, s, p);
-    if (g_gemm_variant == 13) hipLaunchKernelGGL((gemm_kernel<false, false, EPI_BIAS_BF16, 3>), grid, dim3(256), 0, s, p);
-    if (g_gemm_variant == 14) hipLaunchKernelGGL((gemm_kernel<false, false, EPI_BIAS_BF16, 4>), grid, dim3(256), 0, s, p);
-    if (g_gemm_variant == 15) hipLaunchKernelGGL((gemm_kernel<false, false, EPI_BIAS_BF16, 5>), grid, dim3(256), 0, s, p);
-    if (g_gemm_variant == 16) hipLaunchKernelGGL((gemm_kernel<false, false, EPI_BIAS_BF16, 6>), grid, dim3(256), 0, s, p);
-    if (g_gemm_variant == 17) hipLaunchKernelGGL((gemm_kernel<false, false, EPI_BIAS_BF16, 7>), grid, dim3(256), 0, s, p);
-    if (g_gemm_variant == 18) hipLaunchKernelGGL((gemm_kernel<false, false, EPI_BIAS_BF16, 8>), grid, dim3(256), 0, s, p);
-    if (g_gemm_variant == 19) hipLaunchKernelGGL((gemm_kernel<false, false, EPI_BIAS_BF16, 9>), grid, dim3(256), 0, s, p);
-    return check_launch("gemm_kernel<dbg>");
-  }
+  if (!at && !bt && epi == EPI_BIAS_BF16 && v >= 11 && v <= 19) return {PLAN_128, 1, 0, v - 10};
 #endif
-  if (EPI != EPI_SLAB_F32 && p.splitk_ws) {
-    const int rs = (!AT && g_gemm_variant == 0) ? resid_split(p, EPI) : 1;
+  if (epi != EPI_SLAB_F32 && p.splitk_ws) {
     const int sp = rs > 1 ? rs : auto_splits(p, p.splitk_ws_bytes);
     if (sp > 1) {
-      GemmParams q = p;
-      q.K = p.K / sp; q.outf = p.splitk_ws; q.ldc = p.N; q.colsum_part = nullptr;
-      const int pp_npn = split_pp_npn(p, AT, sp);
-      const long chunks = (long)p.M * (p.N >> 3);
-      if (pp_npn) {
-        q.K = p.K;                       // the ping-pong kernel slices K by gridDim.z itself
-        int rc = gemm_pp_launch_slab(q, BT, pp_npn, sp, s);
-        if (rc) return rc;
-        if (defer) return CAREL_OK;          // the caller's next kernel consumes the slabs (GEMM_EX_DEFER_EPILOGUE)
-        hipLaunchKernelGGL((slab_epilogue_kernel<EPI>), dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s, p, (const float*)p.splitk_ws, sp);
-        return check_launch("gemm_pp_kernel split-K + slab_epilogue_kernel");
-      }
-      hipLaunchKernelGGL((gemm_kernel<AT, BT, EPI_SLAB_F32>), dim3(p.tiles_m * p.tiles_n, 1, sp), dim3(256), 0, s, q);
-      if (defer) return check_launch("gemm_kernel split-K (epilogue deferred)");
-      hipLaunchKernelGGL((slab_epilogue_kernel<EPI>), dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s, p, (const float*)p.splitk_ws, sp);
-      return check_launch("gemm_kernel split-K + slab_epilogue_kernel");
+      const int npn = split_pp_npn(p, at, sp);
+      return {npn ? PLAN_PP_SLABS : PLAN_128_SLABS, sp, npn, 0};
     }
   }
-  if (defer) return set_error(CAREL_ERR_ARG, "carel_gemm_bf16: internal: epilogue deferred for a GEMM that does not split (plan / launch disagree)");
-  hipLaunchKernelGGL((gemm_kernel<AT, BT, EPI>), grid, dim3(256), 0, s, p);
-  return check_launch("gemm_kernel");
+  return {PLAN_128, 1, 0, 0};
+}
+
+// One GEMM call, checked and planned (gemm_prepare): what gemm_bf16_ex launches and what the plan queries return
+struct PlannedGemm { GemmParams p; int splits; GemmPlan plan; int (*launch)(const PlannedGemm&, hipStream_t); };
+// Executes a plan: the launches of its kernel family and, for the slab families, the slab epilogue behind them -- unless the caller takes
+// the slabs over (GEMM_EX_DEFER_EPILOGUE)
+template <bool AT, bool BT, int EPI>
+static int launch(const PlannedGemm& g, hipStream_t s) {
+  const GemmParams& p = g.p; const GemmPlan& plan = g.plan; const int splits = g.splits;
+  const bool defer = (p.split_tile_factor & GEMM_EX_DEFER_EPILOGUE) != 0;
+  if (defer && plan.slabs == 1) return set_error(CAREL_ERR_ARG, "carel_gemm_bf16: epilogue deferred for a GEMM that does not split (ask gemm_bf16_split_plan first)");
+  const dim3 grid(p.tiles_m * p.tiles_n, 1, splits);
+  switch (plan.family) {
+    case PLAN_PP:
+#ifdef CAREL_GEMM_ABLATE
+      if (plan.dbg) return AT ? gemm_pp_launch_tn_dbg(p, plan.npn, splits, plan.dbg, s) : gemm_pp_launch_dbg(p, plan.npn, plan.dbg, s);
+#endif
+      return AT ? gemm_pp_launch_tn(p, plan.npn, splits, s) : gemm_pp_launch(p, BT, EPI, plan.npn, s);
+#ifdef CAREL_EXPERIMENTS
+    case PLAN_PAIR: return gemm_pp_launch_pair(p, BT, EPI, s);
+    case PLAN_TRI: return gemm_tri_launch(p, EPI, s);
+#endif
+    case PLAN_BIG: return launch_big<AT, BT, EPI>(p, splits, s);
+    case PLAN_128:
+#ifdef CAREL_GEMM_ABLATE
+      if constexpr (!AT && !BT && EPI == EPI_BIAS_BF16) {
+        if (plan.dbg == 1) hipLaunchKernelGGL((gemm_kernel<false, false, EPI_BIAS_BF16, 1>), grid, dim3(256), 0, s, p);
+        if (plan.dbg == 2) hipLaunchKernelGGL((gemm_kernel<false, false, EPI_BIAS_BF16, 2>), grid, dim3(256), 0, s, p);
+        if (plan.dbg == 3) hipLaunchKernelGGL((gemm_kernel<false, false, EPI_BIAS_BF16, 3>), grid, dim3(256), 0, s, p);
+        if (plan.dbg == 4) hipLaunchKernelGGL((gemm_kernel<false, false, EPI_BIAS_BF16, 4>), grid, dim3(256), 0, s, p);
+        if (plan.dbg == 5) hipLaunchKernelGGL((gemm_kernel<false, false, EPI_BIAS_BF16, 5>), grid, dim3(256), 0, s, p);
+        if (plan.dbg == 6) hipLaunchKernelGGL((gemm_kernel<false, false, EPI_BIAS_BF16, 6>), grid, dim3(256), 0, s, p);
+        if (plan.dbg == 7) hipLaunchKernelGGL((gemm_kernel<false, false, EPI_BIAS_BF16, 7>), grid, dim3(256), 0, s, p);
+        if (plan.dbg == 8) hipLaunchKernelGGL((gemm_kernel<false, false, EPI_BIAS_BF16, 8>), grid, dim3(256), 0, s, p);
+        if (plan.dbg == 9) hipLaunchKernelGGL((gemm_kernel<false, false, EPI_BIAS_BF16, 9>), grid, dim3(256), 0, s, p);
+        if (plan.dbg) return check_launch("gemm_kernel<dbg>");
+      }
+#endif
+      hipLaunchKernelGGL((gemm_kernel<AT, BT, EPI>), grid, dim3(256), 0, s, p);
+      return check_launch("gemm_kernel");
+#ifdef CAREL_EXPERIMENTS
+    case PLAN_SM:
+      if (plan.slabs == 1) return gemm_sm_launch(p, BT, EPI, 1, s);
+      [[fallthrough]];
+#endif
+    case PLAN_PP_SLABS: case PLAN_128_SLABS:
+      // plan.slabs K slices into fp32 slabs in the workspace, then one pass that sums them and applies the epilogue
+      if constexpr (!AT && EPI != EPI_SLAB_F32) {
+        GemmParams q = p;
+        q.K = p.K / plan.slabs; q.outf = p.splitk_ws; q.ldc = p.N; q.colsum_part = nullptr;
+        int rc = CAREL_OK;
+        if (plan.family == PLAN_PP_SLABS) {
+          q.K = p.K;                       // the ping-pong kernel slices K by gridDim.z itself
+          rc = gemm_pp_launch_slab(q, BT, plan.npn, plan.slabs, s);
+#ifdef CAREL_EXPERIMENTS
+        } else if (plan.family == PLAN_SM) {
+          rc = gemm_sm_launch(q, BT, EPI_SLAB_F32, plan.slabs, s);
+#endif
+        } else {
+          hipLaunchKernelGGL((gemm_kernel<AT, BT, EPI_SLAB_F32>), dim3(p.tiles_m * p.tiles_n, 1, plan.slabs), dim3(256), 0, s, q);
+        }
+        if (rc) return rc;
+        if (!defer) {                      // (deferred: the caller's next kernel consumes the slabs)
+          const long chunks = (long)p.M * (p.N >> 3);
+          hipLaunchKernelGGL((slab_epilogue_kernel<EPI>), dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s, p, (const float*)p.splitk_ws, plan.slabs);
+        }
+        return check_launch("split-K GEMM + slab_epilogue_kernel");
+      }
+      [[fallthrough]];
+    default: return set_error(CAREL_ERR_ARG, "carel_gemm_bf16: internal: no launch for plan family %d", plan.family);
+  }
+}
+// the instance of launch() for a form and an epilogue; null: the library has no such GEMM
+static decltype(PlannedGemm::launch) launch_instance(int form, int epi) {
+#define INSTANCE(AT, BT, EPI) case EPI: return launch<AT, BT, EPI>
+  if (form == CAREL_GEMM_NT) {
+    switch (epi) { INSTANCE(false, false, EPI_BIAS_BF16); INSTANCE(false, false, EPI_BIAS_GELU); INSTANCE(false, false, EPI_BIAS_GELU_DG);
+                   INSTANCE(false, false, EPI_BIAS_DROP_RESID); INSTANCE(false, false, EPI_ADD_F32); }
+  } else if (form == CAREL_GEMM_NN) {
+    switch (epi) { INSTANCE(false, true, EPI_BIAS_BF16); INSTANCE(false, true, EPI_DGELU_BF16); INSTANCE(false, true, EPI_MUL_BF16); INSTANCE(false, true, EPI_ADD_F32); }
+  }
+#undef INSTANCE
+  return form == CAREL_GEMM_TN && epi == EPI_SLAB_F32 ? launch<true, true, EPI_SLAB_F32> : nullptr;
 }
 
 // Sum `splits` fp32 slabs [splits][n] -> out[n] (+ optional accumulate into out)
@@ -688,7 +723,7 @@ __global__ void prof_empty_kernel() {}
 struct ProfScope {
   hipStream_t s; bool active;
   ProfScope(hipStream_t st, double fl) : s(st), active(false) {
-    if (!g_prof.on || fl < 0.0 || g_prof.used + 2 > g_prof.ev.size()) return;
+    if (!g_prof.on || g_prof.used + 2 > g_prof.ev.size()) return;
     if (!g_prof.calibrated) {        // once, on the stream being profiled: what an event pair around a kernel costs by itself
       g_prof.calibrated = true;
       for (size_t i = 0; i + 1 < g_prof.cal.size(); i += 2) {
@@ -848,29 +883,7 @@ extern "C" int carel_gemm_set_variant(int32_t v) {
 }
 #endif   // CAREL_EXPERIMENTS
 
-extern "C" int carel_gemm_bf16(const carel_gemm_args* a, void* stream_) { return carel::gemm_bf16_ex(a, 1, stream_); }
-
-int carel::gemm_bf16_split_plan(const carel_gemm_args* a, int split_tile_factor) {
-  tl_split_plan = 1;
-  if (carel::gemm_bf16_ex(a, (split_tile_factor & ~GEMM_EX_DEFER_EPILOGUE) | GEMM_EX_PLAN_ONLY, nullptr)) return 1;
-  return tl_split_plan;
-}
-
-#ifdef CAREL_EXPERIMENTS
-// the plan-only pass above with the kernel family and tile width it decided on (tests/test_packed_dispatch.py)
-extern "C" int carel_gemm_split_plan(const carel_gemm_args* a, int32_t flags, int32_t* plan) {
-  if (!plan) return set_error(CAREL_ERR_ARG, "carel_gemm_split_plan: null plan");
-  if (flags & ~(0xff | GEMM_EX_FIXED_ROWS)) return set_error(CAREL_ERR_ARG, "carel_gemm_split_plan: flags are a chain count | CAREL_PLAN_FIXED_ROWS");
-  tl_split_plan = 1; tl_plan_family = 0; tl_plan_npn = 0;
-  const int rc = carel::gemm_bf16_ex(a, (flags ? flags : 1) | GEMM_EX_PLAN_ONLY, nullptr);
-  if (rc) return rc;
-  plan[0] = tl_split_plan; plan[1] = tl_plan_family; plan[2] = tl_plan_npn;
-  return CAREL_OK;
-}
-#endif
-
-int carel::gemm_bf16_ex(const carel_gemm_args* a, int split_tile_factor, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
+static int gemm_prepare(const carel_gemm_args* a, int split_tile_factor, PlannedGemm* out) {
   if (!a) return set_error(CAREL_ERR_ARG, "carel_gemm_bf16: null args");
   const int splits = a->splits > 0 ? a->splits : 1;
   if (!gemm_shape_ok(a->M, a->N, a->K, splits, a->form))
@@ -920,45 +933,41 @@ int carel::gemm_bf16_ex(const carel_gemm_args* a, int split_tile_factor, void* s
     default: return set_error(CAREL_ERR_ARG, "carel_gemm_bf16: unknown epilogue %d", epi);
   }
 #undef NEED
-  ProfScope prof_scope(stream, (split_tile_factor & GEMM_EX_PLAN_ONLY) ? -1.0 : 2.0 * (double)a->M * (double)a->N * (double)a->K);
-  if (form == CAREL_GEMM_NT) {
-    switch (epi) {
-      case EPI_BIAS_BF16: return launch<false, false, EPI_BIAS_BF16>(p, 1, stream);
-      case EPI_BIAS_GELU: return launch<false, false, EPI_BIAS_GELU>(p, 1, stream);
-      case EPI_BIAS_GELU_DG: return launch<false, false, EPI_BIAS_GELU_DG>(p, 1, stream);
-      case EPI_BIAS_DROP_RESID: return launch<false, false, EPI_BIAS_DROP_RESID>(p, 1, stream);
-      case EPI_ADD_F32: return launch<false, false, EPI_ADD_F32>(p, 1, stream);
-    }
-  } else if (form == CAREL_GEMM_NN) {
-    switch (epi) {
-      case EPI_BIAS_BF16: return launch<false, true, EPI_BIAS_BF16>(p, 1, stream);
-      case EPI_DGELU_BF16: return launch<false, true, EPI_DGELU_BF16>(p, 1, stream);
-      case EPI_MUL_BF16: return launch<false, true, EPI_MUL_BF16>(p, 1, stream);
-      case EPI_ADD_F32: return launch<false, true, EPI_ADD_F32>(p, 1, stream);
-    }
-  } else if (form == CAREL_GEMM_TN) {
-    if (epi == EPI_SLAB_F32) {
-      if (g_gemm_variant != 1 && g_gemm_variant != 2) {      // ping-pong kernel: K tiles dealt to the slices as evenly as possible
-        GemmParams q = p;
-        q.K = a->K;
-        const int npn = gemm_pp_pick_tn(q, splits);
-        const long wgs = npn ? (long)(q.M / 256) * (q.N / (96 * npn)) * splits : 0;
-        // (the same floor as gemm_pp_wgrad_splits: whatever carel_gemm_wgrad_splits proposes for this kernel must be taken by it)
-        if ((split_tile_factor & GEMM_EX_PLAN_ONLY) && npn && (g_gemm_variant == 3 || wgs >= 64)) {
-          tl_split_plan = 1; tl_plan_family = PLAN_PP; tl_plan_npn = npn;
-          return CAREL_OK;
-        }
-#ifdef CAREL_GEMM_ABLATE
-        if (npn == 2 && g_gemm_variant >= 61 && g_gemm_variant <= 68) return gemm_pp_launch_tn_dbg(q, npn, splits, g_gemm_variant - 60, stream);
+  const auto fn = launch_instance(form, epi);
+  if (!fn) return set_error(CAREL_ERR_ARG, "carel_gemm_bf16: unsupported form/epilogue combination (%d,%d)", form, epi);
+  *out = PlannedGemm{p, splits, gemm_plan(p, form, epi, splits, a->K), fn};
+  // (the ping-pong weight-gradient kernel takes the WHOLE contraction length and deals its K tiles to the slices itself)
+  if (form == CAREL_GEMM_TN && out->plan.family == PLAN_PP) out->p.K = a->K;
+  if (out->plan.family == PLAN_NONE)
+    return set_error(CAREL_ERR_SHAPE, "carel_gemm_bf16: no kernel of this form takes the shape (M=%d N=%d K=%d splits=%d)", a->M, a->N, a->K, splits);
+  return CAREL_OK;
+}
+
+extern "C" int carel_gemm_bf16(const carel_gemm_args* a, void* stream_) { return carel::gemm_bf16_ex(a, 1, stream_); }
+
+int carel::gemm_bf16_split_plan(const carel_gemm_args* a, int split_tile_factor) {
+  PlannedGemm g;
+  return gemm_prepare(a, split_tile_factor, &g) ? 1 : g.plan.slabs;
+}
+
+#ifdef CAREL_EXPERIMENTS
+// the same plan with the kernel family and tile width (tests/test_packed_dispatch.py)
+extern "C" int carel_gemm_split_plan(const carel_gemm_args* a, int32_t flags, int32_t* plan) {
+  if (!plan) return set_error(CAREL_ERR_ARG, "carel_gemm_split_plan: null plan");
+  if (flags & ~(0xff | GEMM_EX_FIXED_ROWS)) return set_error(CAREL_ERR_ARG, "carel_gemm_split_plan: flags are a chain count | CAREL_PLAN_FIXED_ROWS");
+  PlannedGemm g;
+  if (const int rc = gemm_prepare(a, flags ? flags : 1, &g)) return rc;
+  plan[0] = g.plan.slabs; plan[1] = g.plan.family; plan[2] = g.plan.npn;
+  return CAREL_OK;
+}
 #endif
-        if (npn && (g_gemm_variant == 3 || wgs >= 64)) return gemm_pp_launch_tn(q, npn, splits, stream);
-      }
-      if (a->K % (64 * splits) || !((a->M % 128 == 0 && a->N % 128 == 0) || (a->M % 256 == 0 && a->N % 192 == 0)))
-        return set_error(CAREL_ERR_SHAPE, "carel_gemm_bf16: this (M,N,K,splits) fits neither weight-gradient kernel (M=%d N=%d K=%d splits=%d)", a->M, a->N, a->K, splits);
-      return launch<true, true, EPI_SLAB_F32>(p, splits, stream);
-    }
-  }
-  return set_error(CAREL_ERR_ARG, "carel_gemm_bf16: unsupported form/epilogue combination (%d,%d)", form, epi);
+
+int carel::gemm_bf16_ex(const carel_gemm_args* a, int split_tile_factor, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  PlannedGemm g;
+  if (const int rc = gemm_prepare(a, split_tile_factor, &g)) return rc;
+  ProfScope prof_scope(stream, 2.0 * (double)a->M * (double)a->N * (double)a->K);
+  return g.launch(g, stream);
 }
 
 // Split-K factor for the weight gradient dW[M,N] = dY^T X over T tokens (the slab buffer must hold that many [M][N] planes,

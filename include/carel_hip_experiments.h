@@ -60,10 +60,14 @@ int carel_gemm_rowln_pack(const void* W, int64_t ldb, int32_t K, void* out, void
  * must be non-null and aligned as for a launch).  flags: the number of equal GEMMs the caller runs side by side (the forward pass's
  * chains, 1 or 2) | CAREL_PLAN_FIXED_ROWS when M does not depend on the batch (the [CLS]-only last layer).  plan[3] = { fp32 slabs of
  * the internal split-K path (1 = single pass), kernel family CAREL_PLAN_*, tile width in units of 96 columns (ping-pong kernel; else 0) }.
+ * The plan comes from the decision function carel_gemm_bf16 itself launches from, so it holds under every carel_gemm_set_variant state
+ * (forced kernels, CAREL_PLAN_PAIR / CAREL_PLAN_TRI for the pair split-K and three-group kernels when their hooks are on); a call that
+ * carel_gemm_bf16 would refuse is refused here with the same error.
  * carel_encoder_workspace_bytes: the bytes the encoder gives that path (which = 0) and the weight-gradient slab area (which = 1).
  * ---------------------------------------------------------------------------------------------- */
 #define CAREL_PLAN_FIXED_ROWS 0x100
-enum { CAREL_PLAN_PP = 1, CAREL_PLAN_128 = 2, CAREL_PLAN_BIG = 3, CAREL_PLAN_PP_SLABS = 4, CAREL_PLAN_128_SLABS = 5, CAREL_PLAN_SM = 6 };
+enum { CAREL_PLAN_PP = 1, CAREL_PLAN_128 = 2, CAREL_PLAN_BIG = 3, CAREL_PLAN_PP_SLABS = 4, CAREL_PLAN_128_SLABS = 5, CAREL_PLAN_SM = 6,
+       CAREL_PLAN_PAIR = 7, CAREL_PLAN_TRI = 8 };
 int carel_gemm_split_plan(const carel_gemm_args* args, int32_t flags, int32_t* plan);
 int64_t carel_encoder_workspace_bytes(int32_t batch, int32_t seq_len, int32_t which);
 

@@ -8,9 +8,9 @@ so that retuning a constant that moves a regime boundary makes this test name th
 Decisions in the tuple, for the three-layer packed step the sweep runs (full layers 0 and 1, [CLS]-only layer 2):
   * every forward / data-gradient GEMM with M = T rows, as the encoder issues it (encoder.hip forward_layers /
     carel_encoder_backward_layer: same form, epilogue, N, K, residual-LayerNorm inputs, chain count and split-K workspace bytes):
-    (fp32 slabs of the internal split-K path, kernel family, ping-pong tile width npn) from carel_gemm_split_plan, the plan-only
-    pass the encoder itself runs (gemm.hip auto_splits, split_pp_npn, gemm_pp_pick with g_pp_min_tiles / g_pp_min_tiles_k768,
-    resid_split, big_auto).  A slab count > 1 on the FFN1 / QKV data gradient or the out-projection / FFN2 forward is also the
+    (fp32 slabs of the internal split-K path, kernel family, ping-pong tile width npn) from carel_gemm_split_plan, the plan
+    the encoder itself asks for and every launch executes (gemm.hip gemm_plan: auto_splits, split_pp_npn, gemm_pp_pick with
+    g_pp_min_tiles / g_pp_min_tiles_k768, resid_split, big_auto).  A slab count > 1 on the FFN1 / QKV data gradient or the out-projection / FFN2 forward is also the
     decision to defer the slab epilogue into the LayerNorm behind it, and the next layer's `dx_in_slabs`;
   * the weight gradients: whether the grouped launch runs (carel_gemm_wgrad_group_ws_bytes against the encoder's slab area,
     carel_encoder_workspace_bytes) and its workspace (the grouped launch's K-split factor), else the split factor of each
@@ -31,7 +31,7 @@ from carel_vae_amd import _lib as L
 EH, EI = 768, 3072
 B, S = 64, 128
 T_ALL = list(range(128, B * S + 1, 128))
-_BIG = 1 << 40              # a fake, aligned address: the plan-only pass checks the operands' alignment but never reads them
+_BIG = 1 << 40              # a fake, aligned address: the plan checks the operands' alignment but never reads them
 
 
 def _plan(lib, form, epi, M, N, K, flags=1, ws_bytes=0, lnres=False, splits=1):
@@ -124,6 +124,28 @@ def test_the_plan_sees_the_regime_boundaries_the_encoder_is_tuned_for(exp_lib):
     assert all(d[k][0] == 1 and d[k][1] == 1 for k in d if k.startswith(("fwd_", "bwd_"))), d
     assert d["wgrad_group"] is not None and d["wgrad_group"] <= exp_lib.carel_encoder_workspace_bytes(B, S, 1)
     assert [decisions(exp_lib, T)["ln_bwd_rows_per_wave"] for T in (2048, 2176, 4096, 4224)] == [1, 2, 2, 4]
+
+
+def test_the_plan_is_true_under_hooks(exp_lib):
+    """carel_gemm_split_plan reports what carel_gemm_bf16 launches when a kernel is forced (carel_gemm_set_variant 1 / 2 / 3), not
+    "not planned": 1792 x 2304 are multiples of the 128 x 128 and of the 256 x 192 tile, and no forced variant splits along K."""
+    PLAN_PP, PLAN_128, PLAN_BIG = 1, 2, 3          # CAREL_PLAN_* (include/carel_hip_experiments.h)
+
+    def plan():
+        return _plan(exp_lib, L.GEMM_NT, L.EPI_BIAS_BF16, 1792, 2304, 768, ws_bytes=1 << 26)
+
+    before = plan()
+    try:
+        L.check(exp_lib.carel_gemm_set_variant(1))
+        assert plan() == (1, PLAN_128, 0)
+        L.check(exp_lib.carel_gemm_set_variant(2))
+        assert plan() == (1, PLAN_BIG, 0)
+        L.check(exp_lib.carel_gemm_set_variant(3))
+        forced_pp = plan()
+        assert forced_pp[:2] == (1, PLAN_PP) and 1 <= forced_pp[2] <= 3, forced_pp
+    finally:
+        L.check(exp_lib.carel_gemm_set_variant(0))
+    assert plan() == before
 
 
 def test_split_plan_refuses_launch_flags(exp_lib):
