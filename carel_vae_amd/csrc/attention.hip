@@ -9,106 +9,15 @@
 //            and the probability tile is directly the B operand of O^T = V^T P^T (no LDS round trip).
 // Backward : per wave 32 keys (key on the lane).  S and dP accumulators are directly the B operands of
 //            dV^T = dO^T P and dK^T = Q^T dS; dS^T crosses LDS once for dQ^T = K^T dS^T.
-// K/V/Q/dO tiles are LDS images with 128-B rows filled by global_load_lds_dwordx4; the XOR swizzle
-// f_att serves both the row reads (ds_read_b128) and the transposed reads (ds_read_b64_tr_b16).
-#include "carel_hip_internal.h"
+// K/V/Q/dO tiles are LDS images with 128-B rows filled by global_load_lds_dwordx4 (attention_device.h: the layout, its readers and
+// the kernel parameters, shared with attention_long.hip).
+#include "attention_device.h"
 
 namespace carel {
-
-constexpr int HD = 64;        // head dim
-constexpr int NH = 12;        // heads
-constexpr int HID = NH * HD;  // 768
-constexpr int QKV_LD = 3 * HID;
-
-__device__ __forceinline__ int f_att(int row) { return (((row >> 1) & 1) << 2) | ((row >> 2) & 3); }
-__device__ __forceinline__ int att_off(int row, int chunk) { return row * 128 + ((chunk ^ f_att(row)) << 4); }
-
-// fill an image of `rows` x 64 bf16 from a row-major global matrix (row stride ld elements); 256 threads
-__device__ __forceinline__ void stage_att(const bf16_t* __restrict__ g, long ld, int rows, char* img) {
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  for (int q = wave; q < (rows >> 3); q += 4) {
-    const int r = q * 8 + (lane >> 3);
-    const int c = (lane & 7) ^ f_att(r);
-    __builtin_amdgcn_global_load_lds(g + (long)r * ld + c * 8, (CAREL_LDS void*)(img + q * 1024), 16, 0, 0);
-  }
-}
-
-// 32x32x16 operand whose own-matrix row is on the lane: X[row = r0 + (l&31)][kk = 16*s + 8*(l>>5) + j]
-__device__ __forceinline__ bf16x8 frag32_row(const char* img, int r0, int s) {
-  const int l = threadIdx.x & 63;
-  return *(const bf16x8*)(img + att_off(r0 + (l & 31), 2 * s + (l >> 5)));
-}
-// 32x32x16 operand read TRANSPOSED from an image M[kk][x]: lane holds M[kk(j)][x = x0 + (l&31)].
-//   PERM = false: kk(j) = kb + 8*(l>>5) + j                      (natural order)
-//   PERM = true : kk(j) = kb + 8*(j>>2) + 4*(l>>5) + (j&3)        (pairs with an accumulator tile used as
-//                                                                  the other operand, carel_common.h)
-template <bool PERM>
-__device__ __forceinline__ bf16x8 frag32_tr(const char* img, int x0, int kb) {
-  const int l = threadIdx.x & 63;
-  const int g = l >> 4, hh = g >> 1, qq = (l & 15) >> 2, p = l & 3;
-  const int chunk = ((x0 + 16 * (g & 1)) >> 3) + (p >> 1), sub = (p & 1) * 8;
-  const int r0 = PERM ? (kb + 4 * hh + qq) : (kb + 8 * hh + qq);
-  const int r1 = PERM ? (r0 + 8) : (r0 + 4);
-  s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((CAREL_LDS s16x4*)(img + att_off(r0, chunk) + sub));
-  s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((CAREL_LDS s16x4*)(img + att_off(r1, chunk) + sub));
-  s16x8 r = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-  return __builtin_bit_cast(bf16x8, r);
-}
-
-// registers 8s..8s+7 of a 32x32 accumulator as the bf16 B operand of k-step s (rows of the tile = kk)
-__device__ __forceinline__ bf16x8 acc_as_operand(const f32x16& x, int s) {
-  const uint4 r = {pack2bf(x[8 * s], x[8 * s + 1]), pack2bf(x[8 * s + 2], x[8 * s + 3]), pack2bf(x[8 * s + 4], x[8 * s + 5]), pack2bf(x[8 * s + 6], x[8 * s + 7])};
-  return __builtin_bit_cast(bf16x8, r);
-}
-
-__device__ __forceinline__ bf16x8 load_frag_global(const bf16_t* p) { return *(const bf16x8*)p; }
-
-
-// A wave's [32 rows][64 d] result sits in two 32x32 accumulators with the ROW on the lane and 4-element groups of d spread over
-// the registers and the two half-waves: stored straight from there every instruction writes 16-byte fragments of 32 different
-// rows (8 instructions per 128-byte line; measured: the stores were 27 % of the backward kernel).  Through a 4-KiB LDS slot of the
-// wave's own (XOR-swizzled 16-byte chunks: conflict-free both ways) every instruction stores 8 whole 128-byte rows instead.
-__device__ __forceinline__ void store_rows_via_lds(const f32x16 (&acc)[2], float scale, char* slot, bf16_t* grow0, long ld, int row_base, int nrows_live) {
-  const int l = threadIdx.x & 63, r = l & 31, hh = l >> 5;
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int d = dt * 32 + 8 * i + 4 * hh;                          // 4 consecutive d
-      const int chunk = (d >> 3) ^ ((r >> 1) & 7);
-      const uint2 v = {pack2bf(acc[dt][4 * i] * scale, acc[dt][4 * i + 1] * scale), pack2bf(acc[dt][4 * i + 2] * scale, acc[dt][4 * i + 3] * scale)};
-      *(uint2*)(slot + r * 128 + chunk * 16 + (d & 4) * 2) = v;
-    }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                   // the slot is this wave's own: no barrier needed
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int row = it * 8 + (l >> 3), c = l & 7;
-    const uint4 v = *(const uint4*)(slot + row * 128 + ((c ^ ((row >> 1) & 7)) << 4));
-    if (row_base + row < nrows_live) *(uint4*)(grow0 + (long)row * ld + c * 8) = v;
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                   // reads done before the slot is rewritten
-}
-
-struct AttnParams {
-  const bf16_t* qkv;        // [B*S, 2304]
-  const long* att_mask;     // [B, S] (1 = attend) or null
-  bf16_t* ctx;              // fwd out / bwd in  [B*S, 768]
-  float* lse;               // [B, NH, S]
-  const bf16_t* dctx;       // bwd in   [B*S, 768]
-  bf16_t* dqkv;             // bwd out  [B*S, 2304]
-  int B, S;
-  Dropout drop;             // element index ((b*NH + h)*S + q)*S + k
-  const int* cu;            // packed: rows [cu[b], cu[b+1]) belong to sample b (null = dense, rows b*S ..)
-  const float* rel;         // MPNet relative-position bias by distance: [NH][256], entry 127 + (key - query); null = none
-  int qlim;                 // 0 = all; else only the first qlim (multiple of 32) positions of every sample are live queries
-  float* drel;              // bwd: its gradient by distance, [B * NH][256]: row (sample, head) is read-modify-written by that workgroup alone (every
-                            // layer adds to it in stream order) -- no atomics anywhere, so the table gradient is bit-reproducible
-};
 
 #ifndef CAREL_ATTN_ABLATE
 #define CAREL_ATTN_ABLATE 0        // timing ablations of the backward kernel (wrong results): tools/ablate_attn.py
 #endif
-constexpr float MASK_NEG = -3.4028234663852886e38f;   // torch.finfo(float32).min, as HF adds it
 constexpr int ATTN_BWD_LDS = 16384 + 16384 + 32768 + 1024;
 constexpr int ATTN_BWD_LDS_REL = ATTN_BWD_LDS + 1024 + 4096;     // + bias by distance [256] + its gradient, one array per wave [4][256]
 
@@ -125,10 +34,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b = blockIdx.x / NH, h = blockIdx.x - b * NH;
   const int S = p.S;
-  // packed: this sample's `len` tokens start at row cu[b]; tiles may run past them into rows of the next sample
-  // (finite data, masked as keys, never stored as queries)
-  const long row0 = p.cu ? (long)p.cu[b] : (long)b * S;
-  const int len = p.cu ? (p.cu[b + 1] - p.cu[b]) : S;
+  long row0; int len;
+  sample_rows(p, b, row0, len);
   const int nkt = (len + 31) >> 5, rows = nkt << 5;
   const bf16_t* qbase = p.qkv + row0 * QKV_LD + h * HD;
   stage_att(qbase + HID, QKV_LD, rows, kimg);
@@ -168,7 +75,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams p) {
   // softmax over keys: this lane holds, for query q0+(l&31), keys kt*32 + acc32_row(r, lane).  The scores are kept in the log2 domain
   // (scale and log2(e) in one multiply, exp2 instead of exp: one VALU instruction less per element; the backward pass has always recomputed the
   // probabilities that way); a masked key adds finfo.min exactly as HF does, so a sample with no attended key still gets the uniform row.
-  constexpr float SC2 = 0.125f * 1.4426950408889634f;
   float m = -INFINITY;
 #pragma unroll
   for (int kt = 0; kt < 4; ++kt) {
@@ -180,7 +86,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams p) {
         for (int r = 0; r < 16; ++r) {
           const int key = kt * 32 + acc32_row(r, lane);
           float v = fmaf(x[kt][r], SC2, maskadd[key]);
-          if (REL) v = fmaf(relb[127 + key - (q0 + (lane & 31))], 1.4426950408889634f, v);
+          if (REL) v = fmaf(relb[127 + key - (q0 + (lane & 31))], LOG2E, v);
           x[kt][r] = v;
           m = fmaxf(m, v);
         }
@@ -188,7 +94,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           float v = x[kt][r] * SC2;
-          if (REL) v = fmaf(relb[127 + kt * 32 + acc32_row(r, lane) - (q0 + (lane & 31))], 1.4426950408889634f, v);
+          if (REL) v = fmaf(relb[127 + kt * 32 + acc32_row(r, lane) - (q0 + (lane & 31))], LOG2E, v);
           x[kt][r] = v;
           m = fmaxf(m, v);
         }
@@ -200,21 +106,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams p) {
   // dropout_hash2's argument for key 0 (32-bit wrap-around arithmetic, as the element index is defined); keys kt*32 + acc32_row(r) are added per pair
   const uint32_t ebase = (uint32_t)((((long)b * NH + h) * S + (q0 + (lane & 31))) * S) + (uint32_t)(4 * hh) + p.drop.idx_offset;
 #pragma unroll
-  for (int kt = 0; kt < 4; ++kt) {
-    if (kt < nkt) {
-#pragma unroll
-      for (int r = 0; r < 16; r += 2) {          // keys acc32_row(r), acc32_row(r + 1) are an aligned pair: one hash (ebase, S and the offset are even: attn_prepare)
-        const float e0 = __builtin_amdgcn_exp2f(x[kt][r] - m), e1 = __builtin_amdgcn_exp2f(x[kt][r + 1] - m);
-        lsum += e0; lsum += e1;
-        float d0 = 1.0f, d1 = 1.0f;
-        if constexpr (DROP) {       // (a template parameter: tested at run time, every pair sat in its own basic block)
-          const uint32_t hsh = mix32(((ebase + (uint32_t)(kt * 32 + (r & 3) + 8 * (r >> 2))) >> 1) ^ p.drop.key);
-          d0 = dropout_pick(p.drop, hsh, 0u); d1 = dropout_pick(p.drop, hsh, 1u);
-        }
-        x[kt][r] = e0 * d0; x[kt][r + 1] = e1 * d1;
-      }
-    }
-  }
+  for (int kt = 0; kt < 4; ++kt)
+    if (kt < nkt) exp2_dropout_tile<DROP>(x[kt], m, lsum, ebase + (uint32_t)(kt * 32), p.drop);
   lsum += __shfl_xor(lsum, 32, 64);
   const bool qlive = q0 + (lane & 31) < len;
   if (hh == 0 && qlive) p.lse[((long)b * NH + h) * S + q0 + (lane & 31)] = (m + __builtin_amdgcn_logf(lsum)) * 0.6931471805599453f;      // natural log-sum-exp, as before
@@ -237,6 +130,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams p) {
     }
   }
   // (whole-row stores through an extra 16 KiB of LDS were measured here too: no gain -- 12.6 MB of output against 37.7 MB of input)
+  // (store_row_frags spelt out: through the call the compiler inverts one of this kernel's branches)
   bf16_t* crow = p.ctx + (row0 + q0 + (lane & 31)) * HID + h * HD;
   if (qlive) {
 #pragma unroll
@@ -258,7 +152,6 @@ __device__ __forceinline__ int ds_off(int k, int q) { return k * 256 + ((((q >> 
 // rate tested at run time and `live ? exp(..) : 0` written as conditionals, the compiler (ROCm 7.2) built 48 branches per query tile, each
 // around one ds_read_b32 of lse[q] / delta[q] with its own lgkmcnt(0) -- 32 exposed LDS round trips per tile and wave.  Rows past the sample
 // get lse = +inf instead (exp2(-inf) = 0: the exact zeros the `live` test produced) and masked / past-the-sample keys -inf through the mask term.
-constexpr float LOG2E = 1.4426950408889634f;
 template <bool REL, bool DROP>
 __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];   // ATTN_BWD_LDS (+ REL: 2048) bytes
@@ -272,6 +165,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(AttnParams p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b = blockIdx.x / NH, h = blockIdx.x - b * NH;
   const int S = p.S;
+  // (sample_rows spelt out: called here, the compiler arranges this kernel's prologue differently -- other branches, other registers)
   const long row0 = p.cu ? (long)p.cu[b] : (long)b * S;
   const int len = p.cu ? (p.cu[b + 1] - p.cu[b]) : S;
   const int nt = (len + 31) >> 5, rows = nt << 5;
@@ -368,7 +262,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(AttnParams p) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int r = 4 * i + e;
-          float arg = fmaf(sa[r], 0.125f * LOG2E, madd2 - l4[e]);
+          float arg = fmaf(sa[r], SC2, madd2 - l4[e]);
           if (REL) arg = fmaf(relb[127 + key - (qt * 32 + 8 * i + 4 * hh + e)], LOG2E, arg);
           const float pr = CAREL_ATTN_ABLATE == 3 ? arg : __builtin_amdgcn_exp2f(arg);
           float dm = 1.0f;
@@ -489,15 +383,8 @@ extern "C" int carel_attention_fwd(const carel_attn_args* a, void* stream_) {
   AttnParams p;
   int rc = attn_prepare(a, &p, "carel_attention_fwd", false);
   if (rc) return rc;
-  if (p.S > 128) return attn_long_fwd(a, stream);       // flash-style kernels (attention_long.hip)
-  const bool drop = p.drop.thresh != 0;
-  if (p.rel) {
-    if (drop) hipLaunchKernelGGL((attn_fwd_kernel<true, true>), dim3(p.B * NH), dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((attn_fwd_kernel<true, false>), dim3(p.B * NH), dim3(256), 0, stream, p);
-  } else {
-    if (drop) hipLaunchKernelGGL((attn_fwd_kernel<false, true>), dim3(p.B * NH), dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((attn_fwd_kernel<false, false>), dim3(p.B * NH), dim3(256), 0, stream, p);
-  }
+  if (p.S > 128) return attn_long_fwd(p, stream);       // flash-style kernels (attention_long.hip)
+  ATTN_LAUNCH(attn_fwd_kernel, dim3(p.B * NH), 0, 0, stream, p);
   return check_launch("attn_fwd_kernel");
 }
 
@@ -506,59 +393,8 @@ extern "C" int carel_attention_bwd(const carel_attn_args* a, void* stream_) {
   AttnParams p;
   int rc = attn_prepare(a, &p, "carel_attention_bwd", true);
   if (rc) return rc;
-  if (p.S > 128) return attn_long_bwd(a, stream);
-  static bool attr_set = false;     // idempotent; a benign race sets it twice
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_BWD_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_bwd_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_BWD_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_bwd_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_BWD_LDS_REL);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_bwd_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_BWD_LDS_REL);
-    if (e != hipSuccess) return set_error(CAREL_ERR_HIP, "carel_attention_bwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
-  const bool drop = p.drop.thresh != 0;
-  if (p.rel) {
-    if (drop) hipLaunchKernelGGL((attn_bwd_kernel<true, true>), dim3(p.B * NH), dim3(256), ATTN_BWD_LDS_REL, stream, p);
-    else hipLaunchKernelGGL((attn_bwd_kernel<true, false>), dim3(p.B * NH), dim3(256), ATTN_BWD_LDS_REL, stream, p);
-  } else {
-    if (drop) hipLaunchKernelGGL((attn_bwd_kernel<false, true>), dim3(p.B * NH), dim3(256), ATTN_BWD_LDS, stream, p);
-    else hipLaunchKernelGGL((attn_bwd_kernel<false, false>), dim3(p.B * NH), dim3(256), ATTN_BWD_LDS, stream, p);
-  }
+  if (p.S > 128) return attn_long_bwd(p, a->workspace, a->workspace_bytes, stream);
+  ATTN_DYNAMIC_LDS(attn_bwd_kernel, ATTN_BWD_LDS, ATTN_BWD_LDS_REL);
+  ATTN_LAUNCH(attn_bwd_kernel, dim3(p.B * NH), ATTN_BWD_LDS, ATTN_BWD_LDS_REL, stream, p);
   return check_launch("attn_bwd_kernel");
-}
-
-// ------------------------------------------------------------------------------------------------ MPNet relative positions
-// The learned table is relative_attention_bias.weight [32 buckets][12 heads]; bucket[i] (int32 [256], entry i = distance key - query
-// = i - 127, entry 255 unused) is computed by the caller with the very expression of transformers
-// MPNetEncoder.relative_position_bucket (a float32 log and a truncation: not re-derived here, so no rounding can differ).
-namespace carel {
-__global__ void relpos_expand_kernel(const float* table, const int* bucket, float* dist) {     // -> dist [NH][256]
-  const int h = blockIdx.x, i = threadIdx.x;
-  dist[h * 256 + i] = i < 255 ? table[bucket[i] * NH + h] : 0.f;
-}
-// ddist [batch * NH][256] (one row per (sample, head), see AttnParams.drel) -> dtable [32][NH]: samples in order, distances in order
-__global__ __launch_bounds__(256) void relpos_reduce_kernel(const float* ddist, int batch, const int* bucket, float* dtable, int accumulate) {
-  __shared__ float bydist[256];
-  const int h = blockIdx.x, i = threadIdx.x;
-  float s = 0.f;
-  for (int b = 0; b < batch; ++b) s += ddist[((long)b * NH + h) * 256 + i];
-  bydist[i] = s;
-  __syncthreads();
-  if (i < 32) {
-    float t = 0.f;
-    for (int d = 0; d < 255; ++d) if (bucket[d] == i) t += bydist[d];
-    dtable[i * NH + h] = accumulate ? dtable[i * NH + h] + t : t;
-  }
-}
-}  // namespace carel
-
-extern "C" int carel_relpos_expand(const void* table, const void* bucket, void* dist, void* stream) {
-  if (!table || !bucket || !dist) return set_error(CAREL_ERR_ARG, "carel_relpos_expand: null tensor");
-  hipLaunchKernelGGL(relpos_expand_kernel, dim3(NH), dim3(256), 0, (hipStream_t)stream, (const float*)table, (const int*)bucket, (float*)dist);
-  return check_launch("relpos_expand_kernel");
-}
-extern "C" int carel_relpos_reduce(const void* ddist, int32_t batch, const void* bucket, void* dtable, int32_t accumulate, void* stream) {
-  if (!ddist || !bucket || !dtable || batch < 1) return set_error(CAREL_ERR_ARG, "carel_relpos_reduce: null tensor or batch < 1");
-  hipLaunchKernelGGL(relpos_reduce_kernel, dim3(NH), dim3(256), 0, (hipStream_t)stream, (const float*)ddist, (int)batch, (const int*)bucket, (float*)dtable, (int)accumulate);
-  return check_launch("relpos_reduce_kernel");
 }

@@ -17,101 +17,15 @@
 //                         (sample, head, key block); attn_long_drel_kernel adds a (sample, head)'s partials in key-block order to
 //                         its row of d_rel_bias_dist.
 // Bias by distance for S > 128: [12][1024], entry 511 + (key - query) (entry 1023 unused); its gradient [batch * 12][1024], same entry.
-#include "carel_hip_internal.h"
+// The LDS image layout, its fragment readers, the kernel parameters and the softmax tile loop are attention_device.h's, shared with
+// attention.hip.
+#include "attention_device.h"
 
 namespace carel {
 namespace attn_long {
 
-constexpr int HD = 64;
-constexpr int NH = 12;
-constexpr int HID = NH * HD;
-constexpr int QKV_LD = 3 * HID;
 constexpr int SPAN = 1024;              // bias-by-distance row for S > 128
 constexpr int ROFF = SPAN / 2 - 1;      // entry of distance 0
-constexpr float MASK_NEG = -3.4028234663852886e38f;   // torch.finfo(float32).min, as HF adds it
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float SC2 = 0.125f * LOG2E;
-
-// (copies of attention.hip's helpers: that file's kernels stay exactly as they are)
-__device__ __forceinline__ int f_att(int row) { return (((row >> 1) & 1) << 2) | ((row >> 2) & 3); }
-__device__ __forceinline__ int att_off(int row, int chunk) { return row * 128 + ((chunk ^ f_att(row)) << 4); }
-
-// fill an image of `rows` x 64 bf16 (rows a multiple of 8, <= 128) from a row-major global matrix (row stride ld elements); 256 threads
-__device__ __forceinline__ void stage_att(const bf16_t* __restrict__ g, long ld, int rows, char* img) {
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  for (int q = wave; q < (rows >> 3); q += 4) {
-    const int r = q * 8 + (lane >> 3);
-    const int c = (lane & 7) ^ f_att(r);
-    __builtin_amdgcn_global_load_lds(g + (long)r * ld + c * 8, (CAREL_LDS void*)(img + q * 1024), 16, 0, 0);
-  }
-}
-
-__device__ __forceinline__ bf16x8 frag32_row(const char* img, int r0, int s) {
-  const int l = threadIdx.x & 63;
-  return *(const bf16x8*)(img + att_off(r0 + (l & 31), 2 * s + (l >> 5)));
-}
-template <bool PERM>
-__device__ __forceinline__ bf16x8 frag32_tr(const char* img, int x0, int kb) {
-  const int l = threadIdx.x & 63;
-  const int g = l >> 4, hh = g >> 1, qq = (l & 15) >> 2, p = l & 3;
-  const int chunk = ((x0 + 16 * (g & 1)) >> 3) + (p >> 1), sub = (p & 1) * 8;
-  const int r0 = PERM ? (kb + 4 * hh + qq) : (kb + 8 * hh + qq);
-  const int r1 = PERM ? (r0 + 8) : (r0 + 4);
-  s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((CAREL_LDS s16x4*)(img + att_off(r0, chunk) + sub));
-  s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((CAREL_LDS s16x4*)(img + att_off(r1, chunk) + sub));
-  s16x8 r = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-  return __builtin_bit_cast(bf16x8, r);
-}
-__device__ __forceinline__ bf16x8 acc_as_operand(const f32x16& x, int s) {
-  const uint4 r = {pack2bf(x[8 * s], x[8 * s + 1]), pack2bf(x[8 * s + 2], x[8 * s + 3]), pack2bf(x[8 * s + 4], x[8 * s + 5]), pack2bf(x[8 * s + 6], x[8 * s + 7])};
-  return __builtin_bit_cast(bf16x8, r);
-}
-__device__ __forceinline__ bf16x8 load_frag_global(const bf16_t* p) { return *(const bf16x8*)p; }
-
-// a wave's [32 rows][64 d] result (two 32x32 accumulators, row on the lane) stored as whole 128-byte rows through a 4-KiB LDS slot of its own
-__device__ __forceinline__ void store_rows_via_lds(const f32x16 (&acc)[2], float scale, char* slot, bf16_t* grow0, long ld, int row_base, int nrows_live) {
-  const int l = threadIdx.x & 63, r = l & 31, hh = l >> 5;
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int d = dt * 32 + 8 * i + 4 * hh;
-      const int chunk = (d >> 3) ^ ((r >> 1) & 7);
-      const uint2 v = {pack2bf(acc[dt][4 * i] * scale, acc[dt][4 * i + 1] * scale), pack2bf(acc[dt][4 * i + 2] * scale, acc[dt][4 * i + 3] * scale)};
-      *(uint2*)(slot + r * 128 + chunk * 16 + (d & 4) * 2) = v;
-    }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int row = it * 8 + (l >> 3), c = l & 7;
-    const uint4 v = *(const uint4*)(slot + row * 128 + ((c ^ ((row >> 1) & 7)) << 4));
-    if (row_base + row < nrows_live) *(uint4*)(grow0 + (long)row * ld + c * 8) = v;
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-}
-
-struct Params {
-  const bf16_t* qkv;        // [rows, 2304]
-  const long* att_mask;     // [B, S] (1 = attend) or null
-  bf16_t* ctx;              // fwd out / bwd in  [rows, 768]
-  float* lse;               // [B, NH, S]
-  const bf16_t* dctx;       // bwd in
-  bf16_t* dqkv;             // bwd out [rows, 2304]
-  int B, S;
-  Dropout drop;             // element index ((b*NH + h)*S + q)*S + k
-  const int* cu;            // packed: rows [cu[b], cu[b+1]) belong to sample b (null = dense)
-  const float* rel;         // [NH][1024], entry 511 + key - query; null = none
-  int qlim;                 // 0 = all queries; else only the first qlim (multiple of 32) positions are live queries
-  float* delta;             // bwd workspace: [B * NH * S] rowsum(dO * O)
-  float* drel_part;         // bwd workspace (REL): [B * NH][nkb][1024] bias-gradient partials per key block
-  float* drel;              // bwd: [B * NH][1024], added to
-  int nqb, nkb;             // query / key blocks of 128 per (sample, head) in the grid
-};
-
-__device__ __forceinline__ void sample_rows(const Params& p, int b, long& row0, int& len) {
-  row0 = p.cu ? (long)p.cu[b] : (long)b * p.S;
-  len = p.cu ? (p.cu[b + 1] - p.cu[b]) : p.S;
-}
 
 // -------------------------------------------------------------------------------------------------------- forward
 template <bool REL, bool DROP>
@@ -198,17 +112,7 @@ __global__ __launch_bounds__(256, 2) void attn_long_fwd_kernel(Params p) {
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) {
       if (kt < ktl) {
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-          const float e0 = __builtin_amdgcn_exp2f(x[kt][r] - m), e1 = __builtin_amdgcn_exp2f(x[kt][r + 1] - m);
-          lsum += e0; lsum += e1;
-          float d0 = 1.0f, d1 = 1.0f;
-          if constexpr (DROP) {
-            const uint32_t hsh = mix32(((ebase + (uint32_t)(k0 + kt * 32 + (r & 3) + 8 * (r >> 2))) >> 1) ^ p.drop.key);
-            d0 = dropout_pick(p.drop, hsh, 0u); d1 = dropout_pick(p.drop, hsh, 1u);
-          }
-          x[kt][r] = e0 * d0; x[kt][r + 1] = e1 * d1;
-        }
+        exp2_dropout_tile<DROP>(x[kt], m, lsum, ebase + (uint32_t)(k0 + kt * 32), p.drop);
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
           const bf16x8 pf = acc_as_operand(x[kt], s);
@@ -223,17 +127,7 @@ __global__ __launch_bounds__(256, 2) void attn_long_fwd_kernel(Params p) {
   const bool qlive = q < len;
   if (hh == 0 && qlive) p.lse[((long)b * NH + h) * S + q] = (m + __builtin_amdgcn_logf(lsum)) * 0.6931471805599453f;
   const float inv = 1.0f / lsum;
-  bf16_t* crow = p.ctx + (row0 + q) * HID + h * HD;
-  if (qlive) {
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int d = dt * 32 + 8 * i + 4 * hh;
-        uint2 v = {pack2bf(o[dt][4 * i] * inv, o[dt][4 * i + 1] * inv), pack2bf(o[dt][4 * i + 2] * inv, o[dt][4 * i + 3] * inv)};
-        *(uint2*)(crow + d) = v;
-      }
-  }
+  if (qlive) store_row_frags(o, inv, p.ctx + (row0 + q) * HID + h * HD, hh);
 }
 
 // -------------------------------------------------------------------------------------------------------- backward, dQ (+ delta)
@@ -344,16 +238,7 @@ __global__ __launch_bounds__(256, 2) void attn_long_dq_kernel(Params p) {
     }
   }
   if (!qact) return;
-  if (q < len) {
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int d = dt * 32 + 8 * i + 4 * hh;
-        uint2 v = {pack2bf(dq[dt][4 * i] * 0.125f, dq[dt][4 * i + 1] * 0.125f), pack2bf(dq[dt][4 * i + 2] * 0.125f, dq[dt][4 * i + 3] * 0.125f)};
-        *(uint2*)(out + (long)(lane & 31) * QKV_LD + d) = v;
-      }
-  }
+  if (q < len) store_row_frags(dq, 0.125f, out + (long)(lane & 31) * QKV_LD, hh);
 }
 
 // -------------------------------------------------------------------------------------------------------- backward, dK / dV
@@ -544,76 +429,39 @@ extern "C" int64_t carel_attention_bwd_workspace_bytes(int32_t batch, int32_t se
 }
 
 namespace carel {
-// called by attention.hip for seq_len > 128 (its checks have run: heads, head_dim, batch, tensors, q_rows, the dropout offset and
-// the 32-bit element index)
-int attn_long_prepare(const carel_attn_args* a, Params* p, const char* who, bool bwd) {
-  p->qkv = (const bf16_t*)a->qkv; p->att_mask = (const long*)a->attention_mask; p->ctx = (bf16_t*)a->ctx;
-  p->lse = (float*)a->lse; p->dctx = (const bf16_t*)a->dctx; p->dqkv = (bf16_t*)a->dqkv;
-  p->B = a->batch; p->S = a->seq_len; p->cu = (const int*)a->cu_seqlens;
-  p->rel = (const float*)a->rel_bias_dist; p->drel = (float*)a->d_rel_bias_dist;
-  p->qlim = a->q_rows >= a->seq_len ? 0 : a->q_rows;
-  p->drop = make_dropout(a->drop_seed, a->drop_site, a->drop_p, a->drop_idx_offset);
-  p->nqb = n_blocks(a->seq_len); p->nkb = p->nqb;
-  if (p->qlim) p->nqb = n_blocks(p->qlim);
-  p->delta = nullptr; p->drel_part = nullptr;
-  if (bwd) {
-    const int64_t need = carel_attention_bwd_workspace_bytes(a->batch, a->seq_len, p->rel ? 1 : 0);
-    if (!a->workspace || a->workspace_bytes < need)
-      return set_error(CAREL_ERR_ARG, "%s: seq_len %d needs a workspace of carel_attention_bwd_workspace_bytes() = %lld bytes (got %lld)", who,
-                       a->seq_len, (long long)need, (long long)a->workspace_bytes);
-    p->delta = (float*)a->workspace;
-    if (p->rel) p->drel_part = (float*)((char*)a->workspace + delta_bytes(a->batch, a->seq_len));
-  }
-  return CAREL_OK;
+// Called by attention.hip for seq_len > 128 with the parameters attn_prepare has checked and filled; what is added here is the grid's
+// block counts and, in the backward, the workspace's two arrays.
+static Params long_params(const AttnParams& q) {
+  Params p;
+  static_cast<AttnCommon&>(p) = q;
+  p.drel = q.drel;
+  p.nqb = n_blocks(p.S); p.nkb = p.nqb;
+  if (p.qlim) p.nqb = n_blocks(p.qlim);
+  p.delta = nullptr; p.drel_part = nullptr;
+  return p;
 }
 
-int attn_long_fwd(const carel_attn_args* a, hipStream_t stream) {
-  Params p;
-  int rc = attn_long_prepare(a, &p, "carel_attention_fwd", false);
-  if (rc) return rc;
-  const bool drop = p.drop.thresh != 0;
-  const dim3 grid(p.B * NH * p.nqb);
-  if (p.rel) {
-    if (drop) hipLaunchKernelGGL((attn_long_fwd_kernel<true, true>), grid, dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((attn_long_fwd_kernel<true, false>), grid, dim3(256), 0, stream, p);
-  } else {
-    if (drop) hipLaunchKernelGGL((attn_long_fwd_kernel<false, true>), grid, dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((attn_long_fwd_kernel<false, false>), grid, dim3(256), 0, stream, p);
-  }
+int attn_long_fwd(const AttnParams& q, hipStream_t stream) {
+  const Params p = long_params(q);
+  ATTN_LAUNCH(attn_long_fwd_kernel, dim3(p.B * NH * p.nqb), 0, 0, stream, p);
   return check_launch("attn_long_fwd_kernel");
 }
 
-int attn_long_bwd(const carel_attn_args* a, hipStream_t stream) {
-  Params p;
-  int rc = attn_long_prepare(a, &p, "carel_attention_bwd", true);
-  if (rc) return rc;
-  static bool attr_set = false;     // idempotent; a benign race sets it twice
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_long_dkv_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, DKV_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_long_dkv_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, DKV_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_long_dkv_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, DKV_LDS_REL);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_long_dkv_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, DKV_LDS_REL);
-    if (e != hipSuccess) return set_error(CAREL_ERR_HIP, "carel_attention_bwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
-  const bool drop = p.drop.thresh != 0;
+int attn_long_bwd(const AttnParams& q, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
+  Params p = long_params(q);
+  const int64_t need = carel_attention_bwd_workspace_bytes(p.B, p.S, p.rel ? 1 : 0);
+  if (!workspace || workspace_bytes < need)
+    return set_error(CAREL_ERR_ARG, "%s: seq_len %d needs a workspace of carel_attention_bwd_workspace_bytes() = %lld bytes (got %lld)",
+                     "carel_attention_bwd", p.S, (long long)need, (long long)workspace_bytes);
+  p.delta = (float*)workspace;
+  if (p.rel) p.drel_part = (float*)((char*)workspace + delta_bytes(p.B, p.S));
   p.nqb = p.nkb;                    // the dQ pass covers every query block: rows past q_rows get their zeros there
-  const dim3 gq(p.B * NH * p.nqb), gk(p.B * NH * p.nkb);
-  if (p.rel) {
-    if (drop) hipLaunchKernelGGL((attn_long_dq_kernel<true, true>), gq, dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((attn_long_dq_kernel<true, false>), gq, dim3(256), 0, stream, p);
-  } else {
-    if (drop) hipLaunchKernelGGL((attn_long_dq_kernel<false, true>), gq, dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((attn_long_dq_kernel<false, false>), gq, dim3(256), 0, stream, p);
-  }
+  ATTN_DYNAMIC_LDS(attn_long_dkv_kernel, DKV_LDS, DKV_LDS_REL);
+  int rc;
+  const dim3 grid(p.B * NH * p.nkb);
+  ATTN_LAUNCH(attn_long_dq_kernel, grid, 0, 0, stream, p);
   if ((rc = check_launch("attn_long_dq_kernel"))) return rc;
-  if (p.rel) {
-    if (drop) hipLaunchKernelGGL((attn_long_dkv_kernel<true, true>), gk, dim3(256), DKV_LDS_REL, stream, p);
-    else hipLaunchKernelGGL((attn_long_dkv_kernel<true, false>), gk, dim3(256), DKV_LDS_REL, stream, p);
-  } else {
-    if (drop) hipLaunchKernelGGL((attn_long_dkv_kernel<false, true>), gk, dim3(256), DKV_LDS, stream, p);
-    else hipLaunchKernelGGL((attn_long_dkv_kernel<false, false>), gk, dim3(256), DKV_LDS, stream, p);
-  }
+  ATTN_LAUNCH(attn_long_dkv_kernel, grid, DKV_LDS, DKV_LDS_REL, stream, p);
   if ((rc = check_launch("attn_long_dkv_kernel"))) return rc;
   if (p.rel) {
     hipLaunchKernelGGL(attn_long_drel_kernel, dim3(p.B * NH), dim3(256), 0, stream, p);
@@ -623,6 +471,9 @@ int attn_long_bwd(const carel_attn_args* a, hipStream_t stream) {
 }
 }  // namespace carel
 
+// The learned table is relative_attention_bias.weight [32 buckets][12 heads]; bucket[i] (int32 [span], entry i = distance key - query
+// = i - (span/2 - 1), the last entry unused) is computed by the caller with the very expression of transformers
+// MPNetEncoder.relative_position_bucket (a float32 log and a truncation: not re-derived here, so no rounding can differ).
 extern "C" int carel_relpos_expand_span(const void* table, const void* bucket, void* dist, int32_t span, void* stream) {
   if (!table || !bucket || !dist) return set_error(CAREL_ERR_ARG, "carel_relpos_expand_span: null tensor");
   if (span != 256 && span != SPAN) return set_error(CAREL_ERR_ARG, "carel_relpos_expand_span: span must be 256 or 1024 (got %d)", span);
@@ -635,4 +486,13 @@ extern "C" int carel_relpos_reduce_span(const void* ddist, int32_t batch, const 
   hipLaunchKernelGGL(relpos_reduce_span_kernel, dim3(NH), dim3(256), 0, (hipStream_t)stream, (const float*)ddist, (int)batch, (const int*)bucket,
                      (float*)dtable, (int)accumulate, (int)span);
   return check_launch("relpos_reduce_span_kernel");
+}
+// the span-256 forms (S <= 128), as they were before there was a second span
+extern "C" int carel_relpos_expand(const void* table, const void* bucket, void* dist, void* stream) {
+  if (!table || !bucket || !dist) return set_error(CAREL_ERR_ARG, "carel_relpos_expand: null tensor");
+  return carel_relpos_expand_span(table, bucket, dist, 256, stream);
+}
+extern "C" int carel_relpos_reduce(const void* ddist, int32_t batch, const void* bucket, void* dtable, int32_t accumulate, void* stream) {
+  if (!ddist || !bucket || !dtable || batch < 1) return set_error(CAREL_ERR_ARG, "carel_relpos_reduce: null tensor or batch < 1");
+  return carel_relpos_reduce_span(ddist, batch, bucket, dtable, accumulate, 256, stream);
 }

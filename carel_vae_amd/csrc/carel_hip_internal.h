@@ -101,8 +101,10 @@ inline Dropout make_dropout(uint32_t seed, uint32_t site, float p, uint32_t idx_
   return d;
 }
 
-// attention for 128 < seq_len <= 512 (attention_long.hip); carel_attention_fwd / _bwd hand those calls over after their argument checks
-int attn_long_fwd(const carel_attn_args* a, hipStream_t stream);
-int attn_long_bwd(const carel_attn_args* a, hipStream_t stream);
+// attention for 128 < seq_len <= 512 (attention_long.hip); carel_attention_fwd / _bwd hand those calls over with the parameters their
+// argument checks have filled (attention_device.h), the backward with the caller's workspace
+struct AttnParams;
+int attn_long_fwd(const AttnParams& q, hipStream_t stream);
+int attn_long_bwd(const AttnParams& q, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
 }  // namespace carel

@@ -776,11 +776,8 @@ class DrlClassifier(nn.Module):
             span = rel_span(S)
             r = self._rel_buffers(int(a.batch), span)
             lib = L.load()
-            if span == 256:
-                L.check(lib.carel_relpos_expand(self._w(REL_KEY), r.bucket.data_ptr(), r.dist.data_ptr(), L.current_stream()), "carel_relpos_expand")
-            else:
-                L.check(lib.carel_relpos_expand_span(self._w(REL_KEY), r.bucket.data_ptr(), r.dist.data_ptr(), span, L.current_stream()),
-                        "carel_relpos_expand_span")
+            L.check(lib.carel_relpos_expand_span(self._w(REL_KEY), r.bucket.data_ptr(), r.dist.data_ptr(), span, L.current_stream()),
+                    "carel_relpos_expand_span")
             a.rel_bias_dist, a.d_rel_bias_dist = r.dist.data_ptr(), r.ddist.data_ptr()
         return a
 
@@ -788,7 +785,7 @@ class DrlClassifier(nn.Module):
         """MPNet relative positions: bucket[i] = relative_position_bucket(i - (span/2 - 1)) with the expression of transformers
         MPNetEncoder.relative_position_bucket (num_buckets 32, max_distance 128), the bias by distance [12, span] made from the
         learned table before every forward, and the gradient by distance, one row per (sample, head), that the attention backward
-        kernels add into without atomics (bit-reproducible; carel_relpos_reduce sums the samples in order).  span 256 for S <= 128,
+        kernels add into without atomics (bit-reproducible; carel_relpos_reduce_span sums the samples in order).  span 256 for S <= 128,
         1024 for the long-sequence kernels (rel_span)."""
         cache = getattr(self, "_rel_by_span", None)
         if cache is None:
@@ -1148,11 +1145,8 @@ class DrlClassifier(nn.Module):
             layer_ready(0)
         L.check(lib.carel_encoder_backward_embeddings(C.byref(ea), st), "carel_encoder_backward_embeddings")
         if rel is not None:      # fold the gradient by distance (every layer's attention backward added to it) into the table's buckets
-            if span == 256:
-                L.check(lib.carel_relpos_reduce(rel.ddist.data_ptr(), int(ea.batch), rel.bucket.data_ptr(), self._g(REL_KEY), 0, st), "carel_relpos_reduce")
-            else:
-                L.check(lib.carel_relpos_reduce_span(rel.ddist.data_ptr(), int(ea.batch), rel.bucket.data_ptr(), self._g(REL_KEY), 0, span, st),
-                        "carel_relpos_reduce_span")
+            L.check(lib.carel_relpos_reduce_span(rel.ddist.data_ptr(), int(ea.batch), rel.bucket.data_ptr(), self._g(REL_KEY), 0, span, st),
+                    "carel_relpos_reduce_span")
 
     def _bind_grads(self):
         if self._grad_views is None:

@@ -278,6 +278,7 @@ typedef struct carel_attn_args {
 int carel_attention_fwd(const carel_attn_args* args, void* stream);
 int carel_attention_bwd(const carel_attn_args* args, void* stream);
 /* bucket: int32 [256], bucket[i] = relative_position_bucket(i - 127) (entry 255 unused), computed by the caller */
+/* (both are the span-256 calls of carel_relpos_expand_span / carel_relpos_reduce_span below) */
 int carel_relpos_expand(const void* table_f32_32xH, const void* bucket, void* dist_f32_Hx256, void* stream);
 int carel_relpos_reduce(const void* ddist_f32_BHx256, int32_t batch, const void* bucket, void* dtable_f32_32xH, int32_t accumulate, void* stream);
 /* ABI 9: 0 for seq_len <= 128 */

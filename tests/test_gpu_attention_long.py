@@ -206,20 +206,57 @@ def test_long_attention_relative_position_bias(packed):
     assert torch.equal(ddist, first[0]) and torch.equal(dqkv, first[1]) and torch.equal(dtable2, dtable)
 
 
-def test_relpos_span_256_matches_the_original_entry_points():
+def relpos_host(table, bucket, dd, batch, span):
+    """carel_relpos_expand_span / carel_relpos_reduce_span restated on the host in the documented order, every add rounded to float32:
+    dist[h][i] = table[bucket[i]][h] with the last entry 0; the gradient of (head, distance) is the sum over the samples in order
+    starting from 0, and a bucket's is the sum of its distances in ascending order."""
+    dist = np.zeros((NH, span), dtype=np.float32)
+    dtable = np.zeros((32, NH), dtype=np.float32)
+    for h in range(NH):
+        for i in range(span - 1):
+            dist[h, i] = table[bucket[i], h]
+        t = [np.float32(0) for _ in range(32)]
+        for i in range(span - 1):
+            s = np.float32(0)
+            for b in range(batch):
+                s = np.float32(s + dd[b * NH + h, i])
+            t[bucket[i]] = np.float32(t[bucket[i]] + s)
+        for k in range(32):
+            dtable[k, h] = t[k]
+    return torch.from_numpy(dist), torch.from_numpy(dtable)
+
+
+def relpos_span(span, batch, seed):
     lib = L.load()
-    g = torch.Generator().manual_seed(4)
+    g = torch.Generator().manual_seed(seed)
     table = torch.randn((32, NH), generator=g).cuda()
-    rp = O.mpnet_relative_position_bucket(torch.arange(-127, 129)).to(torch.int32).cuda().contiguous()
-    d0, d1 = torch.empty((NH, 256), device="cuda"), torch.empty((NH, 256), device="cuda")
+    half = span // 2
+    rp = O.mpnet_relative_position_bucket(torch.arange(-(half - 1), half + 1)).to(torch.int32).cuda().contiguous()
+    d1 = torch.empty((NH, span), device="cuda")
+    L.check(lib.carel_relpos_expand_span(table.data_ptr(), rp.data_ptr(), d1.data_ptr(), span, L.current_stream()), "expand span")
+    dd = torch.randn((batch * NH, span), generator=g).cuda()
+    t1 = torch.empty((32, NH), device="cuda")
+    L.check(lib.carel_relpos_reduce_span(dd.data_ptr(), batch, rp.data_ptr(), t1.data_ptr(), 0, span, L.current_stream()), "reduce span")
+    torch.cuda.synchronize()
+    d_host, t_host = relpos_host(table.cpu().numpy(), rp.cpu().numpy(), dd.cpu().numpy(), batch, span)
+    assert torch.equal(d1.cpu(), d_host) and torch.equal(t1.cpu(), t_host)
+    return table, rp, dd, d1, t1
+
+
+def test_relpos_span_256_matches_the_original_entry_points():
+    """carel_relpos_expand / carel_relpos_reduce are the span-256 calls of the _span functions: equal bits, and both the bits of the
+    host restatement (relpos_host)."""
+    lib = L.load()
+    table, rp, dd, d1, t1 = relpos_span(256, 3, 4)
+    d0, t0 = torch.empty((NH, 256), device="cuda"), torch.empty((32, NH), device="cuda")
     L.check(lib.carel_relpos_expand(table.data_ptr(), rp.data_ptr(), d0.data_ptr(), L.current_stream()), "expand")
-    L.check(lib.carel_relpos_expand_span(table.data_ptr(), rp.data_ptr(), d1.data_ptr(), 256, L.current_stream()), "expand span")
-    dd = torch.randn((3 * NH, 256), generator=g).cuda()
-    t0, t1 = torch.empty((32, NH), device="cuda"), torch.empty((32, NH), device="cuda")
     L.check(lib.carel_relpos_reduce(dd.data_ptr(), 3, rp.data_ptr(), t0.data_ptr(), 0, L.current_stream()), "reduce")
-    L.check(lib.carel_relpos_reduce_span(dd.data_ptr(), 3, rp.data_ptr(), t1.data_ptr(), 0, 256, L.current_stream()), "reduce span")
     torch.cuda.synchronize()
     assert torch.equal(d0, d1) and torch.equal(t0, t1)
+
+
+def test_relpos_span_1024_matches_the_host_restatement():
+    relpos_span(1024, 2, 5)
 
 
 @pytest.mark.parametrize("p", [0.0, 0.1])
