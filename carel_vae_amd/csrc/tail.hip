@@ -730,7 +730,6 @@ extern "C" int carel_tail_losses(const carel_tail_args* a, void* stream_) {
   const int B = a->batch, D = a->ec_dim, V = a->bow_dim;
   if (V < 1) return set_error(CAREL_ERR_SHAPE, "carel_tail_losses: bow_dim must be positive");
   if (2 * D > DEC_MAXD2) return set_error(CAREL_ERR_SHAPE, "carel_tail_losses: 2*ec_dim must be <= %d", DEC_MAXD2);
-  if (B > 1024) return set_error(CAREL_ERR_SHAPE, "carel_tail_losses: batch must be <= 1024 per rank");
   if (B < 2 && !a->z_global) return set_error(CAREL_ERR_SHAPE, "carel_tail_losses: batch must be >= 2 (MMD divides by n(n-1))");
   if (!a->emo_w || !a->emo_b || !a->cau_w || !a->cau_b || !a->pair_w || !a->pair_b || !a->dec_w || !a->dec_b ||
       !a->emo_labels || !a->cau_labels || !a->pair_labels || !a->bow || !a->eps_e || !a->eps_c || !a->z || !a->terms ||
@@ -775,6 +774,23 @@ extern "C" int carel_tail_losses(const carel_tail_args* a, void* stream_) {
     hipError_t e = hipFuncSetAttribute((const void*)tail_core_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return set_error(CAREL_ERR_HIP, "carel_tail_losses: hipFuncSetAttribute: %s", hipGetErrorString(e));
   }
+  // The decoder's launch plan.  LDS: z + red + weights + tile [B][DEC_J] (+ pass 2: second tile; pass 3: the other groups' dW/db partials).
+  // Together with the check above this is the batch limit of the call: both kernels keep the whole batch in the 160 KB LDS of one CU.
+  const int chunks = (V + DEC_J - 1) / DEC_J;
+  const size_t lds0 = sizeof(float) * ((size_t)B * 2 * D + 16 + (size_t)DEC_J * (2 * D + 1) + (size_t)B * DEC_J);
+  int G = DEC_MAXG;
+  auto lds3_of = [&](int g) { return lds0 + sizeof(float) * (size_t)(g - 1) * DEC_J * (2 * D + 2); };
+  while (G > 1 && (lds3_of(G) > 160 * 1024 || (B + G - 1) / G < 4)) G >>= 1;
+  const size_t lds1 = lds0, lds2 = lds0 + sizeof(float) * (size_t)B * DEC_J, lds3 = lds3_of(G);
+  const size_t ldsmax = lds2 > lds3 ? lds2 : lds3;
+  if (ldsmax > 160 * 1024) return set_error(CAREL_ERR_SHAPE, "carel_tail_losses: batch too large for the decoder kernel (%zu B LDS)", ldsmax);
+  if (ldsmax > 64 * 1024) {
+    hipError_t e = hipSuccess;
+    const void* fns[6] = {(const void*)decoder_kernel<1, 48>, (const void*)decoder_kernel<2, 48>, (const void*)decoder_kernel<3, 48>,
+                          (const void*)decoder_kernel<1, 0>, (const void*)decoder_kernel<2, 0>, (const void*)decoder_kernel<3, 0>};
+    for (int i = 0; i < 6 && e == hipSuccess; ++i) e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsmax);
+    if (e != hipSuccess) return set_error(CAREL_ERR_HIP, "carel_tail_losses: hipFuncSetAttribute: %s", hipGetErrorString(e));
+  }
   c.mmd_part = nullptr; c.mmd_nblk = 0; c.dz_mmd = nullptr;
   // (every shape check comes BEFORE the fork below -- ADVICE r03: an error return between fork and join would leave the side stream un-joined)
   if (c.z_global && c.dis_mode == 0 && (2 * c.n_global + 31) / 32 > MMD_MAX_BLOCKS)
@@ -817,28 +833,12 @@ extern "C" int carel_tail_losses(const carel_tail_args* a, void* stream_) {
   c.prof = g_tail_prof;
   hipLaunchKernelGGL(tail_core_kernel, dim3(1), dim3(1024), lds, core_stream, c);
   if ((rc = check_launch("tail_core_kernel"))) return join_on_error(rc);
-  if (tev && hipEventRecord(tev->join, core_stream) != hipSuccess) return set_error(CAREL_ERR_HIP, "carel_tail_losses: event record failed");
+  if (tev && hipEventRecord(tev->join, core_stream) != hipSuccess) return join_on_error(set_error(CAREL_ERR_HIP, "carel_tail_losses: event record failed"));
 
   DecArgs d;
   d.B = B; d.D2 = 2 * D; d.V = V; d.z = (const float*)a->z; d.w = (const float*)a->dec_w; d.b = (const float*)a->dec_b;
   d.bow = (const float*)a->bow; d.ls = a->label_smoothing; d.part = w.part; d.rowstat = w.rowstat; d.dz_part = w.dz_part;
   d.dw = (float*)a->d_dec_w; d.db = (float*)a->d_dec_b; d.gscale = 1.0f / ((float)B * (float)V);
-  const int chunks = (V + DEC_J - 1) / DEC_J;
-  // LDS: z + red + weights + tile [B][DEC_J] (+ pass 2: second tile; pass 3: the other groups' dW/db partials)
-  const size_t lds0 = sizeof(float) * ((size_t)B * 2 * D + 16 + (size_t)DEC_J * (2 * D + 1) + (size_t)B * DEC_J);
-  int G = DEC_MAXG;
-  auto lds3_of = [&](int g) { return lds0 + sizeof(float) * (size_t)(g - 1) * DEC_J * (2 * D + 2); };
-  while (G > 1 && (lds3_of(G) > 160 * 1024 || (B + G - 1) / G < 4)) G >>= 1;
-  const size_t lds1 = lds0, lds2 = lds0 + sizeof(float) * (size_t)B * DEC_J, lds3 = lds3_of(G);
-  const size_t ldsmax = lds2 > lds3 ? lds2 : lds3;
-  if (ldsmax > 160 * 1024) return set_error(CAREL_ERR_SHAPE, "carel_tail_losses: batch too large for the decoder kernel");
-  if (ldsmax > 64 * 1024) {
-    hipError_t e = hipSuccess;
-    const void* fns[6] = {(const void*)decoder_kernel<1, 48>, (const void*)decoder_kernel<2, 48>, (const void*)decoder_kernel<3, 48>,
-                          (const void*)decoder_kernel<1, 0>, (const void*)decoder_kernel<2, 0>, (const void*)decoder_kernel<3, 0>};
-    for (int i = 0; i < 6 && e == hipSuccess; ++i) e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsmax);
-    if (e != hipSuccess) return set_error(CAREL_ERR_HIP, "carel_tail_losses: hipFuncSetAttribute: %s", hipGetErrorString(e));
-  }
 #define DEC_LAUNCH(PASS, LDS)                                                                              \
   do {                                                                                                  \
     if (2 * D == 48) hipLaunchKernelGGL((decoder_kernel<PASS, 48>), dim3(chunks), dim3(DEC_J * G), LDS, stream, d); \
@@ -850,11 +850,11 @@ extern "C" int carel_tail_losses(const carel_tail_args* a, void* stream_) {
   hipLaunchKernelGGL(decoder_combine_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, (const float*)w.part, chunks, B, 2, w.rowstat);
   DEC_LAUNCH(3, lds3);
 #undef DEC_LAUNCH
-  if ((rc = check_launch("decoder kernels"))) return rc;
+  if ((rc = check_launch("decoder kernels"))) return join_on_error(rc);
   // d(loss)/d lat, unscaled (grad_output is applied in carel_tail_backward)
   // sum the decoder's per-chunk dz partials into slot 0 (in place is safe: block c only reads column c of every part)
   hipLaunchKernelGGL(reduce_parts16_kernel, dim3((B * 2 * D + 15) / 16), dim3(256), 0, stream, (const float*)w.dz_part, w.dz_part, B * 2 * D, chunks);
-  if (tev && hipStreamWaitEvent(stream, tev->join, 0) != hipSuccess) return set_error(CAREL_ERR_HIP, "carel_tail_losses: event join failed");
+  if (tev && hipStreamWaitEvent(stream, tev->join, 0) != hipSuccess) return join_on_error(set_error(CAREL_ERR_HIP, "carel_tail_losses: event join failed"));
   hipLaunchKernelGGL(decoder_total_kernel, dim3(1), dim3(256), 0, stream, (const float*)w.rowstat, B, d.gscale, (float*)a->terms);   // reads terms[0] of the loss kernel
   hipLaunchKernelGGL(tail_dlat_kernel, dim3((B * 2 * D + 255) / 256), dim3(256), 0, stream, (const float*)w.dz_core, (const float*)w.dz_part,
                      1, (const float*)w.dlat_direct, (const float*)a->lat, (const float*)a->eps_e, (const float*)a->eps_c, B, D, 1.0f, w.dlat);

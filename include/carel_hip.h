@@ -407,6 +407,15 @@ int carel_encoder_backward_embeddings(const carel_encoder_args* args, void* stre
  * z_global [global_n, 2*ec_dim] (all-gathered samples) + global_row_offset make the MMD the global-batch
  * statistic, differentiated for the local rows and scaled by mmd_grad_scale (= world size when gradients
  * are averaged over ranks).
+ * Batch limit of carel_tail_losses: its loss kernel (one workgroup) and its decoder kernels keep the whole batch in the 160 KB
+ * LDS of one CU, so the largest batch depends on ec_dim (and, by one sample at most, on e_classes).  At 6 emotion classes:
+ *     ec_dim | decoder accepts B <= | loss kernel accepts B <=
+ *        8   |        142           |        363
+ *       16   |        127           |        211
+ *       24   |        114           |        149
+ *       32   |        101           |        115
+ * The smaller figure holds (any bow_dim).  A larger batch (and batch < 2 without z_global) returns CAREL_ERR_SHAPE before
+ * anything is launched: no output is touched and no work is left on the side stream.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct carel_tail_args {
   int32_t batch, seq_len, hidden, ec_dim, e_classes, bow_dim;
@@ -707,8 +716,8 @@ int carel_vi_upper(const carel_vi_args* args, void* stream);
  * terms[4] = *vae_loss_in + w_entropy * (ec_entropy + ce_entropy), the vae_and_classifier_loss of :275-279.
  * Dropout: the library's counter-based masks at sites 103 (ec_disc's input) and 104 (ce_disc's input), element index
  * (drop_row_offset + b) * ec_dim + k.  Every sum runs in a fixed order (no atomics): the same inputs give the same bits.
- * 1 <= batch <= 1024, 1 <= ec_dim <= 32 (the tail's limits).  Bad arguments return before any HIP call; nothing is
- * allocated and the host is never synchronised.
+ * 1 <= batch <= 1024 (this kernel's own limit; the tail that produces z is tighter, see carel_tail_losses), 1 <= ec_dim <= 32
+ * (the tail's limit).  Bad arguments return before any HIP call; nothing is allocated and the host is never synchronised.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct carel_gan_args {
   const void* z;                     /* f32 [B, 2*ec_dim] (carel_tail_args.z) */

@@ -476,7 +476,7 @@ def hsic_statistic(x, y, s_x=1.0, s_y=1.0):
     m = x.shape[0]
     K = torch.exp(-pw(x) / s_x)
     L = torch.exp(-pw(y) / s_y)
-    Hm = torch.eye(m) - (1.0 / m) * torch.ones((m, m))
+    Hm = torch.eye(m, dtype=x.dtype) - (1.0 / m) * torch.ones((m, m), dtype=x.dtype)
     return torch.trace(L @ (Hm @ (K @ Hm))) / ((m - 1) ** 2)
 
 

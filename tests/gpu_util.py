@@ -146,3 +146,25 @@ def block_rel_err(got, ref, segs, floor=0.05):
         i = int(e.argmax())
         out.append((float(e.flatten()[i]), where[i // ATT_NH] + (i % ATT_NH,)))
     return tuple(out)
+
+
+# ------------------------------------------------------------------------------------------------ guarded output buffers
+GUARD = 160 << 10          # bytes of random guard before and after every output buffer (more than 32 rows of the attention dqkv)
+
+
+class Guarded:
+    """A tensor of `shape` between two GUARD-byte regions of random bytes, in one allocation."""
+
+    def __init__(self, shape, dtype, fill, gen):
+        self.nbytes = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
+        self.buf = torch.empty(2 * GUARD + self.nbytes, dtype=torch.uint8, device="cuda")
+        self.pattern = torch.randint(0, 256, (2, GUARD), generator=gen, dtype=torch.uint8).cuda()
+        self.buf[:GUARD] = self.pattern[0]
+        self.buf[GUARD + self.nbytes:] = self.pattern[1]
+        self.t = self.buf[GUARD:GUARD + self.nbytes].view(dtype).view(shape)
+        self.ptr = self.buf.data_ptr() + GUARD
+        if fill is not None:
+            self.t.fill_(fill)
+
+    def intact(self):
+        return torch.equal(self.buf[:GUARD], self.pattern[0]) and torch.equal(self.buf[GUARD + self.nbytes:], self.pattern[1])

@@ -12,12 +12,11 @@ import torch
 
 from carel_vae_amd import _lib as L
 from oracle import carel_oracle as O
-from tests.gpu_util import attn_ref_fp64, block_rel_err
+from tests.gpu_util import Guarded, attn_ref_fp64, block_rel_err
 
 pytestmark = pytest.mark.gpu
 NH, HD, H = 12, 64, 768
 SEQS = list(range(32, 513, 32))
-GUARD = 160 << 10          # bytes of random guard before and after every output buffer (more than 32 rows of dqkv)
 # 1.5x the worst block errors over this module's cases measured on an MI355X: (blocks at or above the floor of block_rel_err, blocks
 # below it); dtable: per head of the table gradient
 BOUND = {"ctx": (4.8e-3, 2.5e-3), "dq": (0.20, 0.50), "dk": (0.058, 2.6), "dv": (6.7e-3, 5.1e-3), "dtable": (0.026,)}
@@ -28,24 +27,6 @@ def check(name, errs, tag):
     """errs: block_rel_err's ((error, where) of the blocks above its floor, (error, where) of those below)."""
     for (e, where), bound in zip(errs, BOUND[name]):
         assert e <= bound, (name, e, bound, tag, where)
-
-
-class Guarded:
-    """A tensor of `shape` between two GUARD-byte regions of random bytes, in one allocation."""
-
-    def __init__(self, shape, dtype, fill, gen):
-        self.nbytes = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
-        self.buf = torch.empty(2 * GUARD + self.nbytes, dtype=torch.uint8, device="cuda")
-        self.pattern = torch.randint(0, 256, (2, GUARD), generator=gen, dtype=torch.uint8).cuda()
-        self.buf[:GUARD] = self.pattern[0]
-        self.buf[GUARD + self.nbytes:] = self.pattern[1]
-        self.t = self.buf[GUARD:GUARD + self.nbytes].view(dtype).view(shape)
-        self.ptr = self.buf.data_ptr() + GUARD
-        if fill is not None:
-            self.t.fill_(fill)
-
-    def intact(self):
-        return torch.equal(self.buf[:GUARD], self.pattern[0]) and torch.equal(self.buf[GUARD + self.nbytes:], self.pattern[1])
 
 
 def bits_equal(x, y):

@@ -8,55 +8,9 @@ import torch
 from carel_vae_amd import _lib as L
 from carel_vae_amd import ops
 from oracle import carel_oracle as O
+from tests.tail_restate import TAIL_KEYS, hip_tail, oracle_tail, setup
 
 pytestmark = pytest.mark.gpu
-TAIL_KEYS = ["encoder.pooler.dense.weight", "encoder.pooler.dense.bias",
-             "emotion_mu.weight", "emotion_mu.bias", "emotion_log_var.weight", "emotion_log_var.bias",
-             "cause_mu.weight", "cause_mu.bias", "cause_log_var.weight", "cause_log_var.bias",
-             "emotion_classifier.weight", "emotion_classifier.bias", "cause_classifier.weight", "cause_classifier.bias",
-             "pair_classifier.weight", "pair_classifier.bias", "decoder.weight", "decoder.bias"]
-
-
-def setup(B, S, V, seed, all_negative=False):
-    cfg = O.EncoderConfig(layers=0, vocab_size=50)
-    opt = O.Opt(pair_bow_dim=V)
-    P = {k: v for k, v in O.init_params(cfg, opt, seed=seed).items() if k in TAIL_KEYS}
-    g = torch.Generator().manual_seed(seed)
-    P["encoder.pooler.dense.weight"] = torch.randn((768, 768), generator=g) * 0.05
-    x_last = torch.randn((B * S, 768), generator=g)
-    batch = O.synthetic_batch(B, 8, O.EncoderConfig(layers=1, vocab_size=50), V, seed=seed)
-    if all_negative:
-        batch["labels"].zero_(); batch["cau_labels"].zero_()
-    eps_e, eps_c = torch.randn(24, generator=g), torch.randn(24, generator=g)
-    return cfg, opt, P, x_last, batch, eps_e, eps_c
-
-
-def oracle_tail(P, x_last, batch, eps_e, eps_c, opt, B, S, it, train, seed, **kw):
-    Pg = {k: v.clone().requires_grad_(True) for k, v in P.items()}
-    xg = x_last.clone().requires_grad_(True)
-    pooled = torch.tanh(xg.view(B, S, 768)[:, 0] @ Pg["encoder.pooler.dense.weight"].t() + Pg["encoder.pooler.dense.bias"])
-    out = O.tail_forward(Pg, pooled, batch["emo_labels"], batch["cau_labels"], batch["labels"], batch["bow_reps"], it, opt,
-                         eps_e, eps_c, train=train, seed=seed, **kw)
-    out["loss"].backward()
-    return out, pooled, {k: v.grad for k, v in Pg.items()}, xg.grad
-
-
-def hip_tail(P, x_last, batch, eps_e, eps_c, opt, B, S, V, it, drop, serial=0, **kw):
-    dev = "cuda"
-    W = {k: v.to(dev) for k, v in P.items()}
-    G = {k: torch.full_like(v, float("nan")) for k, v in W.items()}
-    buf = ops.TailBuffers(B, S, 24, opt.e_num_class, V, dev)
-    labels = dict(emo=batch["emo_labels"].to(dev).view(-1).contiguous(), cau=batch["cau_labels"].to(dev).view(-1).contiguous(),
-                  pair=batch["labels"].to(dev).view(-1).contiguous(), bow=batch["bow_reps"].to(dev).contiguous())
-    xl = x_last.to(dev)
-    a = ops.tail_args(buf, xl, W, labels, eps_e.to(dev), eps_c.to(dev), opt, ops.kl_anneal_weight(it, opt), grads=G, drop=drop, **kw)
-    a._keep = (W, G, labels, xl)
-    a.serial = serial
-    ops.tail_latents(a)
-    ops.tail_losses(a)
-    ops.tail_backward(a, None)
-    torch.cuda.synchronize()
-    return buf, G
 
 
 @pytest.mark.parametrize("B,V,train", [(64, 23771, True), (8, 257, False)])
