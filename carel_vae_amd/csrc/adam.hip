@@ -12,7 +12,7 @@ struct AdamArgs {
   float lr_over_bc1, inv_sqrt_bc2, b1, b2, eps, grad_scale;
   long skip_lo, skip_hi; const float* skip_flag;     // [skip_lo, skip_hi) untouched when *skip_flag != 0
   const float* skip_count;                           // optional device scalar: steps the skip range has been frozen so far
-  float lr, step;                                    //   -> its bias corrections use (step - *skip_count), like torch's per-parameter step
+  float lr; long step;                               //   -> its bias corrections use (step - *skip_count), like torch's per-parameter step
   const float* grad_scale_dev;                       // optional device scalar multiplied into the gradient (clip coefficient)
   float decay;                                       // AdamW: p *= decay (= 1 - lr * weight_decay) first, inside the decay segments
   const long* seg; int nseg;                         // sorted [start, end) pairs (elements, multiples of 4) that take the decay
@@ -34,11 +34,18 @@ __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, con
 
 // torch.optim.Adam keeps one step counter PER PARAMETER and does not advance it when the parameter's grad is None: the range
 // that can be frozen (the pair head) therefore has its own bias corrections once it has been frozen at least once
+// beta^k in double by repeated squaring (k a small whole number of steps): 1 - powf(0.999f, 2) loses 1.5e-5 of 0.002 to cancellation,
+// a hundred times the rounding of everything else in the update, and the host takes its own corrections from double pow
+__device__ __forceinline__ double adam_pow_steps(double b, long k) {
+  double r = 1.0;
+  for (; k > 0; k >>= 1, b *= b) if (k & 1) r *= b;
+  return r;
+}
 __device__ __forceinline__ AdamArgs adam_range_args(const AdamArgs& a) {
   AdamArgs r = a;
-  const float own = a.step - a.skip_count[0];
-  r.lr_over_bc1 = a.lr / (1.0f - powf(a.b1, own));
-  r.inv_sqrt_bc2 = 1.0f / sqrtf(1.0f - powf(a.b2, own));
+  const long own = a.step - (long)a.skip_count[0];
+  r.lr_over_bc1 = (float)((double)a.lr / (1.0 - adam_pow_steps((double)a.b1, own)));
+  r.inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - adam_pow_steps((double)a.b2, own)));
   return r;
 }
 
@@ -55,11 +62,16 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
   for (; i < a.n; i += stride) {
     if (i + 4 <= a.n) {
       float4 p = *(float4*)(a.p + i);
-      if (a.nseg > 0 && adam_decays(a, i)) { p.x *= a.decay; p.y *= a.decay; p.z *= a.decay; p.w *= a.decay; }   // param.mul_(1 - lr * weight_decay)
       const float4 g = *(const float4*)(a.g + i);
       float4 m = *(float4*)(a.m + i), v = *(float4*)(a.v + i);
       const bool s0 = skipping && i + 0 >= a.skip_lo && i + 0 < a.skip_hi, s1 = skipping && i + 1 >= a.skip_lo && i + 1 < a.skip_hi;
       const bool s2 = skipping && i + 2 >= a.skip_lo && i + 2 < a.skip_hi, s3 = skipping && i + 3 >= a.skip_lo && i + 3 < a.skip_hi;
+      if (a.nseg > 0 && adam_decays(a, i)) {                        // param.mul_(1 - lr * weight_decay): not on a frozen element (grad None)
+        if (!s0) p.x *= a.decay;
+        if (!s1) p.y *= a.decay;
+        if (!s2) p.z *= a.decay;
+        if (!s3) p.w *= a.decay;
+      }
       if (own_steps && i + 3 >= a.skip_lo && i < a.skip_hi) {       // (rare: the few float4 groups that touch the pair head)
         const AdamArgs r = adam_range_args(a);
         const bool r0 = i + 0 >= a.skip_lo && i + 0 < a.skip_hi, r1 = i + 1 >= a.skip_lo && i + 1 < a.skip_hi;
@@ -139,6 +151,7 @@ extern "C" int carel_adam_step(const carel_adam_args* a, void* stream_) {
   if (a->step < 1) return set_error(CAREL_ERR_ARG, "carel_adam_step: step must be >= 1");
   if (((uintptr_t)a->param | (uintptr_t)a->grad | (uintptr_t)a->exp_avg | (uintptr_t)a->exp_avg_sq) & 15)
     return set_error(CAREL_ERR_ARG, "carel_adam_step: buffers must be 16-byte aligned");
+  if ((uintptr_t)a->shadow_bf16 & 7) return set_error(CAREL_ERR_ARG, "carel_adam_step: shadow_bf16 must be 8-byte aligned");
   AdamArgs k;
   k.p = (float*)a->param; k.g = (const float*)a->grad; k.m = (float*)a->exp_avg; k.v = (float*)a->exp_avg_sq;
   k.shadow = (bf16_t*)a->shadow_bf16; k.n = a->n;
@@ -146,7 +159,7 @@ extern "C" int carel_adam_step(const carel_adam_args* a, void* stream_) {
   k.lr_over_bc1 = (float)((double)a->lr / bc1); k.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
   k.b1 = a->beta1; k.b2 = a->beta2; k.eps = a->eps; k.grad_scale = a->grad_scale == 0.f ? 1.f : a->grad_scale;
   k.skip_lo = a->skip_lo; k.skip_hi = a->skip_hi; k.skip_flag = (const float*)a->skip_flag;
-  k.skip_count = (const float*)a->skip_count; k.lr = a->lr; k.step = (float)a->step;
+  k.skip_count = (const float*)a->skip_count; k.lr = a->lr; k.step = (long)a->step;
   k.grad_scale_dev = (const float*)a->grad_scale_dev;
   k.decay = (float)(1.0 - (double)a->lr * (double)a->weight_decay);
   k.seg = (const long*)a->decay_segments; k.nseg = a->decay_segments ? a->n_decay_segments : 0;

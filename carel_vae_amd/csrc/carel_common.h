@@ -74,7 +74,7 @@ __device__ __forceinline__ void dropout_mult_n(const Dropout& d, uint32_t idx, f
   if ((j0 & 1u) == 0u) {
 #pragma unroll
     for (int i = 0; i < N / 2; ++i) {
-      const uint32_t h = mix32(((j0 >> 1) + (uint32_t)i) ^ d.key);
+      const uint32_t h = mix32(((j0 + 2u * (uint32_t)i) >> 1) ^ d.key);       // (the element index wraps at 2^32, so the pair index at 2^31)
       m[2 * i] = dropout_pick(d, h, 0u); m[2 * i + 1] = dropout_pick(d, h, 1u);
     }
   } else {

@@ -579,7 +579,7 @@ int carel_adapter_backward(const carel_adapter_args* args, void* stream);
  * ---------------------------------------------------------------------------------------------- */
 typedef struct carel_adam_args {
   void* param; const void* grad; void* exp_avg; void* exp_avg_sq;   /* f32 [n], 16-byte aligned */
-  void* shadow_bf16;                                                 /* bf16 [n] or NULL */
+  void* shadow_bf16;                                                 /* bf16 [n] or NULL; 8-byte aligned (stored four at a time) */
   int64_t n;
   int64_t step;                       /* 1-based step count (bias correction) */
   float lr, beta1, beta2, eps;

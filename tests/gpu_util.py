@@ -41,6 +41,30 @@ def gemm(A, B, form, epi, M, N, K, splits=1, out_bf16=None, out2_bf16=None, out_
     L.check(L.load().carel_gemm_bf16(C.byref(a), L.current_stream()), "carel_gemm_bf16")
 
 
+def keep_mask(seed, site, n, p, off=0, device="cuda"):
+    """Dropout multipliers (0 or 1/(1-p), float64) of the n elements off .. off + n - 1 (uint32, wrapping) from oracle.dropout_keep."""
+    from oracle import carel_oracle as O
+    idx = (np.arange(n, dtype=np.uint64) + np.uint64(off)).astype(np.uint32)
+    return torch.from_numpy(O.dropout_keep(seed, site, idx, p).astype(np.float64) / (1 - p)).to(device)
+
+
+def bits(t: torch.Tensor) -> torch.Tensor:
+    """The tensor's bits as integers on the CPU, so that torch.equal compares NaNs and signed zeros as bits."""
+    t = t.detach().contiguous().cpu()
+    return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
+
+
+class one_thread:
+    """`with one_thread():` -- torch's CPU ops on one thread (many small tensors: a thread pool only gets in its own way)."""
+
+    def __enter__(self):
+        self.n = torch.get_num_threads()
+        torch.set_num_threads(1)
+
+    def __exit__(self, *a):
+        torch.set_num_threads(self.n)
+
+
 def rel_err(got: torch.Tensor, ref: torch.Tensor) -> float:
     got, ref = got.double().cpu(), ref.double().cpu()
     return float((got - ref).norm() / max(ref.norm().item(), 1e-30))
@@ -168,3 +192,22 @@ class Guarded:
 
     def intact(self):
         return torch.equal(self.buf[:GUARD], self.pattern[0]) and torch.equal(self.buf[GUARD + self.nbytes:], self.pattern[1])
+
+
+class Arena:
+    """The Guarded buffers of one case: nan() hands out a NaN-filled one, put() one holding a copy of `src`; intact() checks them all."""
+
+    def __init__(self, seed=0):
+        self.gen, self.all = torch.Generator().manual_seed(seed), []
+
+    def nan(self, shape, dtype=torch.float32):
+        self.all.append(Guarded(tuple(shape), dtype, float("nan"), self.gen))
+        return self.all[-1]
+
+    def put(self, src):
+        self.all.append(Guarded(tuple(src.shape), src.dtype, None, self.gen))
+        self.all[-1].t.copy_(src)
+        return self.all[-1]
+
+    def intact(self):
+        return all(b.intact() for b in self.all)

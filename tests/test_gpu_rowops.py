@@ -7,7 +7,7 @@ import torch
 
 from carel_vae_amd import _lib as L
 from oracle import carel_oracle as O
-from tests.gpu_util import rel_err
+from tests.gpu_util import keep_mask, rel_err
 
 pytestmark = pytest.mark.gpu
 H = 768
@@ -16,11 +16,6 @@ H = 768
 def _rand(shape, scale=1.0, seed=0):
     g = torch.Generator(device="cpu").manual_seed(seed)
     return (torch.randn(shape, generator=g) * scale).cuda()
-
-
-def keep_mask(seed, site, n, p, off=0):
-    idx = (np.arange(n, dtype=np.uint64) + np.uint64(off)).astype(np.uint32)
-    return torch.from_numpy(O.dropout_keep(seed, site, idx, p).astype(np.float64) / (1 - p)).cuda()
 
 
 @pytest.mark.parametrize("rows", [1000, 2049, 3000, 4100])
