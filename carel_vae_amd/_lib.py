@@ -105,6 +105,13 @@ class AdapterArgs(C.Structure):
                 ("work", C.c_void_p)]
 
 
+class AdapterWgradArgs(C.Structure):
+    """carel_adapter_wgrad_args (include/carel_hip.h)."""
+    _fields_ = [("d_q_w", C.c_void_p * 2), ("d_q_b", C.c_void_p * 2), ("d_k_w", C.c_void_p * 2), ("d_k_b", C.c_void_p * 2),
+                ("d_v_w", C.c_void_p * 2), ("d_v_b", C.c_void_p * 2), ("d_o_w", C.c_void_p * 2), ("d_o_b", C.c_void_p * 2),
+                ("work", C.c_void_p), ("accumulate", C.c_int32)]
+
+
 class AdamArgs(C.Structure):
     _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
                 ("shadow_bf16", C.c_void_p), ("n", C.c_int64), ("step", C.c_int64),
@@ -274,6 +281,8 @@ SIGNATURES = {
     "carel_adapter_build_u": (C.c_int, [C.POINTER(AdapterArgs), C.c_void_p]),
     "carel_adapter_forward": (C.c_int, [C.POINTER(AdapterArgs), C.c_void_p]),
     "carel_adapter_backward": (C.c_int, [C.POINTER(AdapterArgs), C.c_void_p]),
+    "carel_adapter_wgrad_workspace_floats": (C.c_int64, [C.c_int32] * 2),
+    "carel_adapter_backward_weights": (C.c_int, [C.POINTER(AdapterArgs), C.POINTER(AdapterWgradArgs), C.c_void_p]),
     "carel_adam_step": (C.c_int, [C.POINTER(AdamArgs), C.c_void_p]),
     "carel_cast_f32_to_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "carel_rmsprop_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_void_p]),

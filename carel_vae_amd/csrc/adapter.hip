@@ -6,6 +6,8 @@
 //   forward : rowdot (scores of every row against the 2G u vectors)  ->  normalise (one wave per score row)  ->  combine (the p-weighted
 //             row sums, one workgroup per sample and 64 columns)  [-> raw: value projection and out_proj GEMVs]
 //   backward: [raw: out_proj^T and value^T GEMVs]  ->  rowdot (dp = H . dctx)  ->  dzdh (normaliser backward, dH rows)
+//   weights : (opt-in, after the backward)  wgrad_dz (the normaliser backward again, stored)  ->  combine (du partials per sample, the one
+//             pass over H)  ->  wgrad_dusum (samples in ascending order)  ->  gemv (dqv = W_k du)  ->  wgrad_outer (every rank-1 / rank-B product)
 // Every sum has a fixed order; no atomics.
 #include "carel_hip_internal.h"
 
@@ -343,6 +345,88 @@ static void gemvT(AdPtr2 W, const float* in, long i_as, long i_bs, int B, int G,
                      scale, out, o_as, o_bs);
 }
 
+// ---- weight gradients (carel_adapter_backward_weights; opt-in, nothing above calls these) ----
+// dz[r][0..S) = normaliser backward of score row r = k*B + b from p[r] and dp[r]: the expressions of adapter_dzdh_kernel, so that the
+// weight gradients and dH differentiate the same function.  One wave per row.  Grid ceil(rows / 4).
+__global__ __launch_bounds__(256) void adapter_wgrad_dz_kernel(int rows, int S, int mode, const float* __restrict__ p, const float* __restrict__ dp,
+                                                               float* __restrict__ dz) {
+  const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;                     // wave-uniform
+  const float* pr = p + (long)r * S;
+  const float* gr = dp + (long)r * S;
+  const bool v0 = lane < S, v1 = lane + 64 < S;
+  const float p0 = v0 ? pr[lane] : 0.f, p1 = v1 ? pr[lane + 64] : 0.f;
+  const float g0 = v0 ? gr[lane] : 0.f, g1 = v1 ? gr[lane + 64] : 0.f;
+  float r0, r1;
+  if (mode == 0) {
+    const float sp = wave_sum(p0 * g0 + p1 * g1);
+    r0 = p0 * (g0 - sp); r1 = p1 * (g1 - sp);
+  } else if (mode == 1) {
+    const float n = wave_sum((p0 > 0.f ? 1.f : 0.f) + (p1 > 0.f ? 1.f : 0.f));
+    const float mean = wave_sum((p0 > 0.f ? g0 : 0.f) + (p1 > 0.f ? g1 : 0.f)) / n;
+    r0 = p0 > 0.f ? g0 - mean : 0.f; r1 = p1 > 0.f ? g1 - mean : 0.f;
+  } else {
+    const float q0 = sqrtf(p0), q1 = sqrtf(p1);
+    const float d0 = g0 * q0, d1 = g1 * q1;
+    const float qq = wave_sum(d0 + d1) / wave_sum(q0 + q1);
+    r0 = d0 - qq * q0; r1 = d1 - qq * q1;
+  }
+  if (v0) dz[(long)r * S + lane] = r0;
+  if (v1) dz[(long)r * S + lane + 64] = r1;
+}
+
+// du[a][g][:] = scale * sum_b part[a][b][g][:], the samples in ascending order.  Grid ceil(2 G 768 / 256).
+__global__ __launch_bounds__(256) void adapter_wgrad_dusum_kernel(const float* __restrict__ part, int B, int G, float scale, float* __restrict__ du) {
+  const int i = blockIdx.x * 256 + threadIdx.x, per = G * AD;
+  if (i >= 2 * per) return;
+  const int a = i / per;
+  const float* src = part + (long)a * B * per + (i - a * per);
+  float v = 0.f;
+#pragma unroll 8
+  for (int b = 0; b < B; ++b) v += src[(long)b * per];
+  du[i] = v * scale;
+}
+
+// Rank-nb updates, one job per blockIdx.z:
+//   dW_a[n][:] (+)= sum_{b < nb} L_a[b*l_bs + n] * R_a[b*r_bs + (n / seg)*768 + :]      db_a[n] (+)= sum_{b < nb} L_a[b*l_bs + n]
+// (bias 1: that sum; 2: zeros, the key bias; db NULL: none), b ascending; (+)= adds when accumulate, else overwrites.
+// Grid (768 / 8, 2, jobs), 192 threads (one float4 column each); the 8 rows of a workgroup share a head (seg is a multiple of 8).
+constexpr int OW_ROWS = 8;
+struct AdOuterJob { const float* L[2]; const float* R[2]; float* dW[2]; float* db[2]; long l_bs, r_bs; int nb, seg, bias; };
+struct AdOuterJobs { AdOuterJob j[4]; };
+__global__ __launch_bounds__(192) void adapter_wgrad_outer_kernel(AdOuterJobs J, int accumulate) {
+  const AdOuterJob& j = J.j[blockIdx.z];
+  const int a = blockIdx.y, n0 = blockIdx.x * OW_ROWS, t = threadIdx.x;
+  const float* L = j.L[a] + n0;
+  const float* R = j.R[a] + (long)(n0 / j.seg) * AD + t * 4;
+  float4 acc[OW_ROWS];
+#pragma unroll
+  for (int r = 0; r < OW_ROWS; ++r) acc[r] = float4{0.f, 0.f, 0.f, 0.f};
+  for (int b = 0; b < j.nb; ++b) {
+    const float4 r4 = *(const float4*)(R + b * j.r_bs);
+#pragma unroll
+    for (int r = 0; r < OW_ROWS; ++r) {
+      const float l = L[b * j.l_bs + r];
+      acc[r].x = fmaf(l, r4.x, acc[r].x); acc[r].y = fmaf(l, r4.y, acc[r].y);
+      acc[r].z = fmaf(l, r4.z, acc[r].z); acc[r].w = fmaf(l, r4.w, acc[r].w);
+    }
+  }
+  float* dst = j.dW[a] + (long)n0 * AD + t * 4;
+#pragma unroll
+  for (int r = 0; r < OW_ROWS; ++r) {
+    float4 v = acc[r];
+    if (accumulate) { const float4 o = *(const float4*)(dst + (long)r * AD); v.x = o.x + v.x; v.y = o.y + v.y; v.z = o.z + v.z; v.w = o.w + v.w; }
+    *(float4*)(dst + (long)r * AD) = v;
+  }
+  if (j.db[a] && t < OW_ROWS) {
+    float s = 0.f;
+    if (j.bias == 1)
+      for (int b = 0; b < j.nb; ++b) s += L[b * j.l_bs + t];
+    float* d = j.db[a] + n0 + t;
+    *d = accumulate ? *d + s : s;
+  }
+}
+
 struct AdWork { float* qv; float* sc; float* p; float* ctx; float* vcat; float* dvcat; float* dctx; float* part; size_t total; };
 static size_t ad_align(size_t n) { return (n + 63) & ~(size_t)63; }
 static AdWork ad_carve(float* base, int B, int S, int G) {
@@ -352,6 +436,16 @@ static AdWork ad_carve(float* base, int B, int S, int G) {
   w.qv = take(2 * AD); w.sc = take(nv * B * S); w.p = take(nv * B * S);
   w.ctx = take(nv * B * AD); w.vcat = take(2 * (size_t)B * AD); w.dvcat = take(2 * (size_t)B * AD); w.dctx = take(nv * B * AD);
   w.part = take((size_t)GT_C * 2 * (B > 1 ? B : 1) * AD);
+  w.total = o;
+  return w;
+}
+// carel_adapter_backward_weights' own scratch: dz [2G][B][S <= 128], per-sample du partials [2][B][G][768], du [2][G][768], dqv [2][768]
+struct AdWgWork { float* dz; float* part; float* du; float* dqv; size_t total; };
+static AdWgWork adwg_carve(float* base, int B, int G) {
+  AdWgWork w; size_t o = 0;
+  auto take = [&](size_t n) { float* q = base ? base + o : nullptr; o += ad_align(n); return q; };
+  const size_t nv = 2 * (size_t)G;
+  w.dz = take(nv * B * 128); w.part = take(nv * B * AD); w.du = take(nv * AD); w.dqv = take(2 * AD);
   w.total = o;
   return w;
 }
@@ -465,4 +559,67 @@ extern "C" int carel_adapter_backward(const carel_adapter_args* a, void* stream_
   AD_NV_SWITCH(nv, hipLaunchKernelGGL(adapter_dzdh_kernel<NV>, dim3(S / DZ_ROWS, a->batch_padded), dim3(192), 0, stream, S, B, G, a->mode,
                                       (const float*)w.p, (const float*)w.sc, dctx, d_as, d_bs, (const float*)a->u, (float*)a->dx_f32));
   return check_launch("carel_adapter_backward");
+}
+
+extern "C" int64_t carel_adapter_wgrad_workspace_floats(int32_t batch, int32_t heads) {
+  if (batch < 1 || heads < 1) return 0;
+  return (int64_t)adwg_carve(nullptr, batch, heads).total;
+}
+
+extern "C" int carel_adapter_backward_weights(const carel_adapter_args* a, const carel_adapter_wgrad_args* g, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const char* who = "carel_adapter_backward_weights";
+  int rc = ad_check(a, who);
+  if (rc) return rc;
+  if (!g) return set_error(CAREL_ERR_ARG, "%s: null gradient args", who);
+  if (!g->work) return set_error(CAREL_ERR_ARG, "%s: null work", who);
+  if (g->accumulate != 0 && g->accumulate != 1) return set_error(CAREL_ERR_ARG, "%s: accumulate must be 0 or 1", who);
+  if (!a->x_f32) return set_error(CAREL_ERR_ARG, "%s: null x", who);
+  const bool raw = a->mode == 0;
+  if (raw && !a->d_out_f32) return set_error(CAREL_ERR_ARG, "%s: raw mode needs d_out", who);
+  for (int i = 0; i < 2; ++i) {
+    if (!a->query[i] || !a->k_w[i]) return set_error(CAREL_ERR_ARG, "%s: null query / k_w", who);
+    if (!g->d_q_w[i] || !g->d_q_b[i] || !g->d_k_w[i] || !g->d_k_b[i]) return set_error(CAREL_ERR_ARG, "%s: null d_q_* / d_k_*", who);
+    if (raw && (!g->d_v_w[i] || !g->d_v_b[i] || !g->d_o_w[i] || !g->d_o_b[i])) return set_error(CAREL_ERR_ARG, "%s: raw mode needs d_v_* / d_o_*", who);
+    const void* vec[] = {a->query[i], g->d_q_w[i], g->d_k_w[i], raw ? g->d_v_w[i] : nullptr, raw ? g->d_o_w[i] : nullptr};
+    for (const void* q : vec)
+      if ((uintptr_t)q & 15) return set_error(CAREL_ERR_ARG, "%s: query and the weight-gradient destinations must be 16-byte aligned", who);
+  }
+  const int B = a->batch, S = a->seq_len, G = a->heads, nv = 2 * G, dh = AD / G;
+  AdWork w = ad_carve((float*)a->work, B, S, G);
+  AdWgWork gw = adwg_carve((float*)g->work, B, G);
+  const float* x = (const float*)a->x_f32;
+  hipLaunchKernelGGL(adapter_wgrad_dz_kernel, dim3((nv * B + 3) / 4), dim3(256), 0, stream, nv * B, S, a->mode, (const float*)w.p,
+                     (const float*)w.sc, gw.dz);
+  // the one pass over H: per-sample partials du_k(b) = sum_s dz[k][b][s] H[b,s], then the samples in ascending order (x 1/sqrt(d))
+  AD_NV_SWITCH(nv, hipLaunchKernelGGL(adapter_combine_kernel<NV>, dim3(AD / CB_COLS, B), dim3(256), 0, stream, x, S, B, G, (const float*)gw.dz,
+                                      gw.part, (long)B * G * AD, (long)G * AD));
+  hipLaunchKernelGGL(adapter_wgrad_dusum_kernel, dim3((nv * AD + 255) / 256), dim3(256), 0, stream, (const float*)gw.part, B, G,
+                     1.0f / sqrtf((float)dh), gw.du);
+  // dqv[n] = W_k[n,:] . du_head(n)
+  AdPtr2 K = {{(const float*)a->k_w[0], (const float*)a->k_w[1]}, {nullptr, nullptr}};
+  hipLaunchKernelGGL(adapter_gemv_kernel, dim3(AD / 4, 2), dim3(256), 0, stream, K, (const float*)gw.du, (long)G * AD, 0L, dh, 1, gw.dqv, (long)AD, 0L);
+  AdOuterJobs J = {};
+  int nj = 0;
+  for (int i = 0; i < 2; ++i) {
+    AdOuterJob& k = J.j[0]; AdOuterJob& q = J.j[1];
+    k.L[i] = w.qv + i * AD; k.R[i] = gw.du + (long)i * G * AD; k.dW[i] = (float*)g->d_k_w[i]; k.db[i] = (float*)g->d_k_b[i];
+    q.L[i] = gw.dqv + i * AD; q.R[i] = (const float*)a->query[i]; q.dW[i] = (float*)g->d_q_w[i]; q.db[i] = (float*)g->d_q_b[i];
+  }
+  J.j[0].nb = 1; J.j[0].seg = dh; J.j[0].bias = 2;
+  J.j[1].nb = 1; J.j[1].seg = AD; J.j[1].bias = 1;
+  nj = 2;
+  if (raw) {
+    const long ob = (long)B * AD;
+    for (int i = 0; i < 2; ++i) {
+      AdOuterJob& o = J.j[2]; AdOuterJob& v = J.j[3];
+      o.L[i] = (const float*)a->d_out_f32 + i * ob; o.R[i] = w.vcat + i * ob; o.dW[i] = (float*)g->d_o_w[i]; o.db[i] = (float*)g->d_o_b[i];
+      v.L[i] = w.dvcat + i * ob; v.R[i] = w.ctx + (long)i * B * G * AD; v.dW[i] = (float*)g->d_v_w[i]; v.db[i] = (float*)g->d_v_b[i];
+    }
+    J.j[2].nb = B; J.j[2].seg = AD; J.j[2].bias = 1; J.j[2].l_bs = AD; J.j[2].r_bs = AD;
+    J.j[3].nb = B; J.j[3].seg = dh; J.j[3].bias = 1; J.j[3].l_bs = AD; J.j[3].r_bs = (long)G * AD;
+    nj = 4;
+  }
+  hipLaunchKernelGGL(adapter_wgrad_outer_kernel, dim3(AD / OW_ROWS, 2, nj), dim3(192), 0, stream, J, g->accumulate);
+  return check_launch(who);
 }

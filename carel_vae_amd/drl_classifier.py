@@ -177,6 +177,25 @@ def adapter_config(opt):
     return mode, int(heads)
 
 
+def train_adapter_config(opt, adapter):
+    """opt.train_adapter (an extension; the reference's get_params() forgets the adapters, :460-473, so they stay at their random
+    initialisation there): True / False or the strings "true" / "false", as the scripts pass flags.  Absent: False."""
+    v = getattr(opt, "train_adapter", False)
+    if isinstance(v, str) and v in ("true", "false"):
+        v = v == "true"
+    if v is not True and v is not False:
+        raise L.CarelError("opt.train_adapter must be True, False, 'true' or 'false'; got %r" % (v,))
+    if v and adapter == "false":
+        raise L.CarelError("opt.train_adapter needs a sentence adapter (opt.adapter = raw, sparsemax or entmax)")
+    return v
+
+
+# the adapter tensors the forward reads, i.e. the ones opt.train_adapter trains (the sparse subclasses never use in_proj_* / out_proj / v_proj)
+ADAPTER_TRAINED = {"raw": ("in_proj_weight", "in_proj_bias", "out_proj.weight", "out_proj.bias"),
+                   "sparsemax": ("q_proj.weight", "q_proj.bias", "k_proj.weight", "k_proj.bias"),
+                   "entmax": ("q_proj.weight", "q_proj.bias", "k_proj.weight", "k_proj.bias")}
+
+
 class CarelEncoder(nn.Module):
     """Parameter container with the key names of transformers BertModel / RobertaModel."""
 
@@ -431,9 +450,11 @@ class DrlClassifier(nn.Module):
         if opt.bert_dim != H:
             raise L.CarelError("bert_dim must be 768 (BERT-base kernels)")
         self.adapter, self.head_number = adapter_config(opt)
+        self.train_adapter = train_adapter_config(opt, self.adapter)
         self.encoder = CarelEncoder(self.cfg)
         self._aprx_names = []
         self._adapter_names = []
+        self._adapter_train_names = []      # opt.train_adapter: the subset of _adapter_names that gets a gradient and sits in the optimised prefix
         self._disc_names = []               # the two adversaries of opt.disentangle == "gan" (fp32 only, own optimisers)
         self._gan = getattr(opt, "disentangle", "mmd") == "gan"
         self._has_pair_skip = True          # the pair head is frozen for a step whose pair loss was replaced by 0 (ref :510-511)
@@ -470,6 +491,8 @@ class DrlClassifier(nn.Module):
             self.cause_adapter = _Adapter(self.adapter != "raw")
             self._adapter_names = ["%s_adapter.%s" % (side, n) for side in ("emotion", "cause")
                                    for n, _ in getattr(self, side + "_adapter").named_parameters()]
+            if self.train_adapter:
+                self._adapter_train_names = ["%s_adapter.%s" % (side, n) for side in ("emotion", "cause") for n in ADAPTER_TRAINED[self.adapter]]
         self.emotion_mu = _Holder((opt.ec_dim, H))
         self.emotion_log_var = _Holder((opt.ec_dim, H))
         self.cause_mu = _Holder((opt.ec_dim, H))
@@ -502,11 +525,13 @@ class DrlClassifier(nn.Module):
                   "emotion_classifier.weight", "emotion_classifier.bias", "cause_classifier.weight", "cause_classifier.bias"]
         self._pair_range_names = ["pair_classifier.weight", "pair_classifier.bias"]
         order += self._pair_range_names
+        order += self._adapter_train_names   # opt.train_adapter: inside the one range FusedAdam(model) covers
         n_opt_names = len(order)
         order += self._disc_names            # gan: [vae group | ec_disc | ce_disc | latent heads], each optimiser group one contiguous range
         order += ["emotion_mu.weight", "emotion_mu.bias", "emotion_log_var.weight", "emotion_log_var.bias",
                   "cause_mu.weight", "cause_mu.bias", "cause_log_var.weight", "cause_log_var.bias"]
-        order += self._adapter_names         # frozen like the latent heads (absent from get_params() in the reference, :460)
+        # frozen like the latent heads (absent from get_params() in the reference, :460); with opt.train_adapter: the ones the forward never reads
+        order += [k for k in self._adapter_names if k not in self._adapter_train_names]
         order += self._aprx_names            # own optimiser (ref ec_vi :873), fp32 only
         assert set(order) == set(named), "parameter inventory mismatch"
         return order, n_opt_names, named
@@ -591,7 +616,7 @@ class DrlClassifier(nn.Module):
             return list(self.ec_mu.parameters()) + list(self.ec_log_var.parameters()), other
         if self._gan:            # (ec_disc_params, ce_disc_params, other_params), drl_classifier_ec_gan.py:302-317
             return list(self.ec_disc.parameters()), list(self.ce_disc.parameters()), other
-        return other
+        return other + [self._named[k] for k in self._adapter_train_names]     # opt.train_adapter (extension): the reference's list, then the adapters
 
     def make_fused_optimizers(self, adv_lr=None, vae_lr=None, fuse_into_backward=False):
         """opt.disentangle == "gan": the three optimisers of drl_classifier_ec_gan.py's script body (:903-908) as HIP kernels over the flat
@@ -962,6 +987,19 @@ class DrlClassifier(nn.Module):
                 out.append(dict(q_w=m.q_proj.weight.data, q_b=m.q_proj.bias.data, k_w=m.k_proj.weight.data))
         return out
 
+    def _adapter_grads(self):
+        """The destinations of carel_adapter_backward_weights in the flat gradient buffer, keyed like _adapter_weights() with a d_ prefix."""
+        out = []
+        for side in ("emotion", "cause"):
+            g = lambda n: self._grad_view("%s_adapter.%s" % (side, n))        # noqa: E731
+            if self.adapter == "raw":
+                w, b = g("in_proj_weight"), g("in_proj_bias")
+                out.append(dict(d_q_w=w[:H], d_q_b=b[:H], d_k_w=w[H:2 * H], d_k_b=b[H:2 * H], d_v_w=w[2 * H:], d_v_b=b[2 * H:],
+                                d_o_w=g("out_proj.weight"), d_o_b=g("out_proj.bias")))
+            else:
+                out.append(dict(d_q_w=g("q_proj.weight"), d_q_b=g("q_proj.bias"), d_k_w=g("k_proj.weight"), d_k_b=g("k_proj.bias")))
+        return out
+
     def _adapter_forward(self, c, x_last_ptr):
         """Adapter outputs [2, B, 768] from the dense last hidden states.  u is rebuilt on every call (a few microseconds), so a change
         of the queries or adapter weights by any route -- load_state_dict, an in-place edit, a write through .data -- takes effect."""
@@ -1092,6 +1130,8 @@ class DrlClassifier(nn.Module):
         if c.ad is not None:                     # adapter mode: d head_in -> every row of dx_last (the tail left dx_last alone)
             c.ad.dx_f32 = ea.dx
             ops.adapter_backward(c.ad)
+            if self._adapter_train_names:        # opt.train_adapter: overwritten like every gradient of this call (`prev` is added below)
+                ops.adapter_backward_weights(c.ad, ops.adapter_wgrad_args(self._ws[("adapter", c.B, c.S)], self._adapter_grads()))
         # classifier / decoder gradients were produced for grad_output = 1: one contiguous range of the flat buffer
         lo = self._offs["decoder.weight"]
         ops.scale_(self._flat_grad[lo:self._pair_hi], go)
@@ -1151,9 +1191,9 @@ class DrlClassifier(nn.Module):
     def _bind_grads(self):
         if self._grad_views is None:
             self._grad_views = {k: self._grad_view(k) for k in self._order}
-        skip = set(self._aprx_names) | set(self._adapter_names) | set(self._disc_names)
+        skip = set(self._aprx_names) | (set(self._adapter_names) - set(self._adapter_train_names)) | set(self._disc_names)
         for k, p in self._named.items():
-            if k not in skip:               # the approximation net's gradients belong to _AprxLoss.backward (the adversaries': _run_backward_gan); adapters get none (frozen)
+            if k not in skip:               # the approximation net's gradients belong to _AprxLoss.backward (the adversaries': _run_backward_gan); adapters get none (frozen) unless opt.train_adapter
                 p.grad = self._grad_views[k]
 
     # ------------------------------------------------------------------ public API (reference surface)

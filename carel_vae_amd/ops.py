@@ -234,6 +234,7 @@ class AdapterBuffers:
         self.out = torch.empty((2, B, H), **f)
         self.d_out = torch.empty((2, B, H), **f)
         self.work = torch.empty(L.load().carel_adapter_workspace_floats(B, S, heads), **f)
+        self.wgrad_work = None           # carel_adapter_backward_weights' own scratch (opt.train_adapter): allocated by adapter_wgrad_args
 
 
 def adapter_args(mode, heads, queries, weights, u, buf, Bp, x=None, dx=None):
@@ -264,6 +265,29 @@ def adapter_forward(a):
 
 def adapter_backward(a):
     L.check(L.load().carel_adapter_backward(C.byref(a), L.current_stream()), "carel_adapter_backward")
+
+
+def adapter_wgrad_args(buf, grads, accumulate=False):
+    """grads: two dicts (emotion, cause) of contiguous f32 destinations keyed like adapter_args' weights with a d_ prefix: d_q_w, d_q_b,
+    d_k_w, d_k_b [768, 768] / [768] and (raw) d_v_w, d_v_b, d_o_w, d_o_b; buf: the AdapterBuffers of the forward / backward calls (its
+    own scratch for this call is allocated on first use); accumulate: add to the destinations instead of overwriting them."""
+    g = L.AdapterWgradArgs()
+    for i in range(2):
+        for f in ("d_q_w", "d_q_b", "d_k_w", "d_k_b", "d_v_w", "d_v_b", "d_o_w", "d_o_b"):
+            t = grads[i].get(f)
+            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != buf.out.device):
+                raise L.CarelError("adapter gradient destination %s must be a contiguous f32 tensor on the adapter's device" % f)
+            getattr(g, f)[i] = None if t is None else t.data_ptr()
+    if buf.wgrad_work is None:
+        buf.wgrad_work = torch.empty(L.load().carel_adapter_wgrad_workspace_floats(buf.B, buf.heads), device=buf.out.device, dtype=torch.float32)
+    g.work, g.accumulate = buf.wgrad_work.data_ptr(), int(bool(accumulate))
+    g._keep = (grads, buf.wgrad_work)
+    return g
+
+
+def adapter_backward_weights(a, g):
+    """Adapter weight gradients; after adapter_forward(a) and adapter_backward(a), whose workspace regions it reads."""
+    L.check(L.load().carel_adapter_backward_weights(C.byref(a), C.byref(g), L.current_stream()), "carel_adapter_backward_weights")
 
 
 def _vi_args(z, net):

@@ -571,6 +571,31 @@ int carel_adapter_forward(const carel_adapter_args* args, void* stream);
  * Adapter weight gradients are not formed (the reference never applies them: its get_params() leaves the adapters out, :460). */
 int carel_adapter_backward(const carel_adapter_args* args, void* stream);
 
+/* Adapter weight gradients (opt-in: the reference never trains its adapters, so nothing on the reference-parity path calls this).
+ * Call after carel_adapter_forward and carel_adapter_backward with the SAME carel_adapter_args.  The regions of args->work those
+ * calls left must be intact: qv = W_q e + b_q (carel_adapter_build_u), p (forward), dp (the backward's rowdot, in the score region)
+ * and, raw mode, ctx / vcat (forward) and dvcat (backward); args->u, x_f32, d_out_f32, query and k_w are read too.  Nothing of
+ * args->work, dx_f32 or out_f32 is written.  With c = 1/sqrt(768/G), head(n) = n / (768/G), e the fixed query:
+ *   dz[h,b,s]  the normaliser backward, recomputed from p and dp by the expressions of carel_adapter_backward
+ *   du_h       = c * sum_b sum_s dz[h,b,s] H[b,s]      (one pass over H: per-sample partials, then the samples in ascending order)
+ *   dqv[n]     = W_k[n,:] . du_head(n)                  d_k_w[n,:] = qv[n] du_head(n)        d_k_b = 0 (translation invariance)
+ *   d_q_w      = dqv (x) e                              d_q_b = dqv
+ *   raw only:  d_o_w = sum_b d_out[b] (x) vcat[b]       d_o_b = sum_b d_out[b]
+ *              d_v_w[n,:] = sum_b dvcat[b][n] ctx_head(n)[b]                                 d_v_b[n] = sum_b dvcat[b][n]
+ * The queries e get no gradient (b_q already makes qv arbitrary).  f32, every sum in a fixed order, no atomics: a repeated call
+ * gives the same bits.  Destinations per adapter (0 = emotion, 1 = cause), [768, 768] row-major / [768]; d_v_* / d_o_* are read in
+ * raw mode only (may be NULL otherwise).  accumulate: 0 = overwrite, 1 = add to what the destinations hold. */
+typedef struct carel_adapter_wgrad_args {
+  void* d_q_w[2]; void* d_q_b[2];
+  void* d_k_w[2]; void* d_k_b[2];
+  void* d_v_w[2]; void* d_v_b[2];
+  void* d_o_w[2]; void* d_o_b[2];
+  void* work;                        /* f32 [carel_adapter_wgrad_workspace_floats(B, G)]: its own scratch, apart from carel_adapter_args.work */
+  int32_t accumulate;
+} carel_adapter_wgrad_args;
+int64_t carel_adapter_wgrad_workspace_floats(int32_t batch, int32_t heads);
+int carel_adapter_backward_weights(const carel_adapter_args* args, const carel_adapter_wgrad_args* grads, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Fused Adam over a flat parameter buffer.  Replaces torch.optim.Adam(...).step() (ref :936, :842) with
  * torch's defaults and update order (lerp for exp_avg; sqrt(v)/sqrt(bc2) + eps).  Optionally refreshes
