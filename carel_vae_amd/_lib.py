@@ -266,6 +266,8 @@ SIGNATURES = {
     "carel_tail_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "carel_tail_latents": (C.c_int, [C.POINTER(TailArgs), C.c_void_p]),
     "carel_tail_losses": (C.c_int, [C.POINTER(TailArgs), C.c_void_p]),
+    "carel_tail_batch_limit": (C.c_int32, [C.c_int32, C.c_int32]),
+    "carel_tail_losses_tiled": (C.c_int, [C.POINTER(TailArgs), C.c_void_p]),
     "carel_tail_backward": (C.c_int, [C.POINTER(TailArgs), C.c_void_p, C.c_void_p]),
     "carel_tail_profile": (C.c_int, [C.c_void_p]),
     "carel_side_stream": (C.c_void_p, [C.c_int32]),

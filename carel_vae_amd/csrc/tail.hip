@@ -640,16 +640,377 @@ __global__ __launch_bounds__(256) void pair_prob_kernel(const float* __restrict_
   prob[b] = 1.0f / (1.0f + expf(-s));
 }
 
+// ------------------------------------------------------------------------------------------
+// Batch-tiled form of the loss step (carel_tail_losses_tiled): the work of tail_core_kernel from "classifier heads" through
+// "parameter gradients" gridded over slabs of TT_R rows, and the three decoder passes with the batch walked in tiles of TB rows.
+// LDS per workgroup does not depend on the batch.  Whatever couples the batch (the pair label sum behind pos_weight, the divisor
+// of the means, the "dead" decision on the batch-mean pair loss) is that of the whole batch, which takes two phases:
+//   phase 1  logits (kept in the workspace), per-row losses and KL -> per-slab partial sums; dlat_direct
+//   phase 2  totals formed in slab order by every workgroup (same bits everywhere), dlogits, dz = heads + dz_mmd, per-slab
+//            partials of the head parameter gradients; workgroup 0 also writes terms[0..6] and pair_dead
+//   tail_head_grads_kernel adds the parameter-gradient partials in slab order.
+// The MMD is mmd_global_kernel's (on the batch's own z, or on z_global), its partials added in block order in double as on
+// tail_core_kernel's mmd_part branch.  No atomics: every sum has an order fixed by indices.
+// ------------------------------------------------------------------------------------------
+constexpr int TT_R = 64;            // rows per slab
+constexpr int TT_THREADS = 256;
+constexpr int TT_MAX_B = 1024;
+constexpr int TT_MAX_SLABS = TT_MAX_B / TT_R;
+constexpr int TT_MAX_NHW = 8 * 32 + 8 + 32 + 1 + 64 + 1;     // head parameters at ec_dim 32, 8 classes
+
+struct TailTiled {
+  TailCore c;              // c.z: the batch's sampled latents, already written by sample_z_kernel
+  float* lg;               // [B][16] head logits (phase 1 -> phase 2)
+  float* spart;            // [slabs][8]: sums over the slab's rows of the emotion, cause, pair losses and the two KL sums
+  float* hpart;            // [slabs][n_hw] head parameter gradients of the slab's rows
+};
+
+template <int PHASE>
+__global__ __launch_bounds__(TT_THREADS) void tail_heads_kernel(TailTiled q) {
+  const TailCore& a = q.c;
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  float* red = (float*)smem_raw;                 // 64
+  const int B = a.B, D = a.D, D2 = 2 * a.D, D4 = 4 * a.D;
+  float* zl = red + 64;                          // [R][2D] sampled latents of the slab
+  float* mlt = zl + TT_R * D2;                   // [R][4D] dropout multipliers: emotion [D] | cause [D] | pair [2D]
+  float* lg = mlt + TT_R * D4;                   // [R][16] head logits
+  float* elog = lg + TT_R * 16;                  // [R][8] emotion dlogits
+  float* gx = elog + TT_R * 8;                   // [R][2] cause / pair dlogit
+  float* hw = gx + TT_R * 2;                     // head weights, as in tail_core_kernel
+  const int n_emo = a.EC * D;
+  const int o_eb = n_emo, o_cw = o_eb + a.EC, o_cb = o_cw + D, o_pw = o_cb + 1, o_pb = o_pw + D2, n_hw = o_pb + 1;
+  const int t = threadIdx.x;
+  const int r0 = blockIdx.x * TT_R, nr = min(TT_R, B - r0);       // this slab: rows r0 .. r0 + nr - 1
+  const int nslab = gridDim.x;
+
+  for (int e = t; e < nr * D2; e += TT_THREADS) zl[e] = a.z[(long)r0 * D2 + e];
+  for (int e = t; e < nr * D4; e += TT_THREADS) {
+    const int b = r0 + e / D4, k = e % D4;                        // dropout streams by the element index of the whole batch
+    mlt[e] = k < D ? dropout_mult(a.d_emo, b * D + k) : (k < D2 ? dropout_mult(a.d_cau, b * D + (k - D)) : dropout_mult(a.d_pair, b * D2 + (k - D2)));
+  }
+  for (int e = t; e < n_hw; e += TT_THREADS)
+    hw[e] = e < o_eb ? a.emo_w[e] : e < o_cw ? a.emo_b[e - o_eb] : e < o_cb ? a.cau_w[e - o_cw] : e < o_pw ? a.cau_b[0]
+          : e < o_pb ? a.pair_w[e - o_pw] : a.pair_b[0];
+  if (PHASE == 2) for (int e = t; e < nr * 16; e += TT_THREADS) lg[e] = q.lg[(long)r0 * 16 + e];
+  __syncthreads();
+  if (PHASE == 1) {
+    // ---- classifier heads: 16 threads per sample, one per logit (emotion classes, cause, pair)
+    for (int e = t; e < nr * 16; e += TT_THREADS) {
+      const int b = e >> 4, h = e & 15;
+      float s = 0.f;
+      if (h < a.EC) {
+        s = hw[o_eb + h];
+        for (int k = 0; k < D; ++k) s = fmaf(hw[h * D + k], zl[b * D2 + k] * mlt[b * D4 + k], s);
+      } else if (h == a.EC) {
+        s = hw[o_cb];
+        for (int k = 0; k < D; ++k) s = fmaf(hw[o_cw + k], zl[b * D2 + D + k] * mlt[b * D4 + D + k], s);
+      } else if (h == a.EC + 1) {
+        s = hw[o_pb];
+        for (int k = 0; k < D2; ++k) s = fmaf(hw[o_pw + k], zl[b * D2 + k] * mlt[b * D4 + D2 + k], s);
+      }
+      lg[e] = s;
+      q.lg[(long)r0 * 16 + e] = s;
+    }
+  }
+  // ---- pos_weight of the whole batch: label sum in an order fixed by the index (or the override)
+  float ysum = 0.f;
+  for (int b = t; b < B; b += TT_THREADS) ysum += a.pair_labels[b];
+  ysum = block_sum(ysum, red);                    // (its barriers also publish lg)
+  const float ntot = a.label_sum_override ? a.n_override : (float)B;
+  float ytot = ysum;
+  if (a.label_sum_override) {
+    ytot = a.label_sum_override[0];
+    for (int r = 1; r < a.label_sum_ranks; ++r) ytot += a.label_sum_override[(long)r * a.rank_stride];
+  }
+  const float pw = (ntot - ytot) / ytot;          // inf when there is no positive in the batch
+  if (PHASE == 1) {
+    float l_emo = 0.f, l_cau = 0.f, l_pair = 0.f;
+    for (int b = t; b < nr; b += TT_THREADS) {
+      const int bg = r0 + b;
+      if (!a.emo_bce) {
+        float mx = -INFINITY;
+        for (int c = 0; c < a.EC; ++c) mx = fmaxf(mx, lg[b * 16 + c]);
+        float se = 0.f;
+        for (int c = 0; c < a.EC; ++c) se += expf(lg[b * 16 + c] - mx);
+        const float lse = mx + logf(se);
+        long lab = a.emo_labels[bg]; lab = lab < 0 ? 0 : (lab >= a.EC ? a.EC - 1 : lab);
+        l_emo += lse - lg[b * 16 + lab];
+      } else {
+        const float pe = 1.0f / (1.0f + expf(-lg[b * 16]));
+        const float te = (float)a.emo_labels[bg] * (1.f - a.ls) + a.ls;
+        l_emo += -(te * fmaxf(logf(pe), -100.f) + (1.f - te) * fmaxf(logf(1.f - pe), -100.f));
+      }
+      const float pc = 1.0f / (1.0f + expf(-lg[b * 16 + a.EC]));
+      const float tc = a.cau_labels[bg] * (1.f - a.ls) + a.ls;
+      l_cau += -(tc * fmaxf(logf(pc), -100.f) + (1.f - tc) * fmaxf(logf(1.f - pc), -100.f));
+      const float xp = lg[b * 16 + a.EC + 1];
+      const float tp = a.pair_labels[bg] * (1.f - a.ls) + a.ls;
+      const float lw = (pw - 1.f) * tp + 1.f;
+      l_pair += (1.f - tp) * xp + lw * (log1pf(expf(-fabsf(xp))) + fmaxf(-xp, 0.f));
+    }
+    l_emo = block_sum(l_emo, red);
+    l_cau = block_sum(l_cau, red);
+    l_pair = block_sum(l_pair, red);
+    // ---- KL (:525-534) and its direct gradient on lat
+    float kle = 0.f, klc = 0.f;
+    for (int e = t; e < nr * D; e += TT_THREADS) {
+      const int b = r0 + e / D, k = e % D;
+      const float* row = a.lat + (long)b * 4 * D;
+      const float mue = row[k], lve = row[D + k], muc = row[2 * D + k], lvc = row[3 * D + k];
+      kle += -0.5f * (1.f + lve - expf(lve) - mue * mue);
+      klc += -0.5f * (1.f + lvc - expf(lvc) - muc * muc);
+      float* dl = a.dlat_direct + (long)b * 4 * D;
+      dl[k] = a.kl_w * mue / B; dl[D + k] = a.kl_w * (-0.5f) * (1.f - expf(lve)) / B;
+      dl[2 * D + k] = a.kl_w * muc / B; dl[3 * D + k] = a.kl_w * (-0.5f) * (1.f - expf(lvc)) / B;
+    }
+    kle = block_sum(kle, red);
+    klc = block_sum(klc, red);
+    if (t == 0) {
+      float* sp = q.spart + blockIdx.x * 8;
+      sp[0] = l_emo; sp[1] = l_cau; sp[2] = l_pair; sp[3] = kle; sp[4] = klc;
+    }
+    return;
+  }
+  // ---- phase 2: the totals of the batch in slab order (every thread of every workgroup forms the same sums)
+  float l_emo = 0.f, l_cau = 0.f, l_pair = 0.f, kle = 0.f, klc = 0.f;
+  for (int s = 0; s < nslab; ++s) {
+    const float* sp = q.spart + s * 8;
+    l_emo += sp[0]; l_cau += sp[1]; l_pair += sp[2]; kle += sp[3]; klc += sp[4];
+  }
+  l_emo = l_emo / B; l_cau = l_cau / B; l_pair = l_pair / B;
+  kle = kle / B * a.kl_w; klc = klc / B * a.kl_w;
+  const bool dead = isinf(l_pair);
+  if (dead) l_pair = 0.f;
+  for (int b = t; b < nr; b += TT_THREADS) {
+    const int bg = r0 + b;
+    if (!a.emo_bce) {
+      float mx = -INFINITY;
+      for (int c = 0; c < a.EC; ++c) mx = fmaxf(mx, lg[b * 16 + c]);
+      float se = 0.f;
+      for (int c = 0; c < a.EC; ++c) se += expf(lg[b * 16 + c] - mx);
+      const float lse = mx + logf(se);
+      long lab = a.emo_labels[bg]; lab = lab < 0 ? 0 : (lab >= a.EC ? a.EC - 1 : lab);
+      for (int c = 0; c < a.EC; ++c) elog[b * 8 + c] = (expf(lg[b * 16 + c] - lse) - (c == lab ? 1.f : 0.f)) * (a.w_emo / B);
+    } else {
+      const float pe = 1.0f / (1.0f + expf(-lg[b * 16]));
+      const float te = (float)a.emo_labels[bg] * (1.f - a.ls) + a.ls;
+      const float gpe = (pe - te) / fmaxf((1.f - pe) * pe, 1e-12f);
+      elog[b * 8] = gpe * pe * (1.f - pe) * (a.w_emo / B);
+    }
+    const float pc = 1.0f / (1.0f + expf(-lg[b * 16 + a.EC]));
+    const float tc = a.cau_labels[bg] * (1.f - a.ls) + a.ls;
+    const float gp = (pc - tc) / fmaxf((1.f - pc) * pc, 1e-12f);
+    gx[b * 2] = gp * pc * (1.f - pc) * (a.w_cau / B);
+    const float xb = lg[b * 16 + a.EC + 1], tb = a.pair_labels[bg] * (1.f - a.ls) + a.ls;
+    const float lw = (pw - 1.f) * tb + 1.f;
+    const float sg = 1.0f / (1.0f + expf(-xb));
+    gx[b * 2 + 1] = dead ? 0.f : ((1.f - tb) - lw * (1.f - sg)) * (a.w_pair / B);
+  }
+  __syncthreads();
+  // ---- dz = d(statistic)/dz + the three heads
+  for (int e = t; e < nr * D2; e += TT_THREADS) {
+    const int b = e / D2, k = e - b * D2;
+    float g = hw[o_pw + k] * gx[b * 2 + 1] * mlt[b * D4 + D2 + k];
+    if (k < D) {
+      float s = 0.f;
+      for (int c = 0; c < a.EC; ++c) s = fmaf(hw[c * D + k], elog[b * 8 + c], s);
+      g += s * mlt[b * D4 + k];
+    } else {
+      g += hw[o_cw + (k - D)] * gx[b * 2] * mlt[b * D4 + k];
+    }
+    const float g0 = a.dz_mmd ? a.dz_mmd[(long)r0 * D2 + e] : 0.f;
+    a.dz[(long)r0 * D2 + e] = g0 + g;
+  }
+  // ---- head parameter gradients of this slab's rows: thread per parameter element, rows in order
+  float* hp = q.hpart + (long)blockIdx.x * n_hw;
+  for (int e = t; e < n_hw; e += TT_THREADS) {
+    float s = 0.f;
+    if (e < o_eb) {
+      const int c = e / D, k = e - c * D;
+      for (int b = 0; b < nr; ++b) s = fmaf(elog[b * 8 + c], zl[b * D2 + k] * mlt[b * D4 + k], s);
+    } else if (e < o_cw) {
+      const int c = e - o_eb;
+      for (int b = 0; b < nr; ++b) s += elog[b * 8 + c];
+    } else if (e < o_cb) {
+      const int k = e - o_cw;
+      for (int b = 0; b < nr; ++b) s = fmaf(gx[b * 2], zl[b * D2 + D + k] * mlt[b * D4 + D + k], s);
+    } else if (e == o_cb) {
+      for (int b = 0; b < nr; ++b) s += gx[b * 2];
+    } else if (e < o_pb) {
+      const int k = e - o_pw;
+      for (int b = 0; b < nr; ++b) s = fmaf(gx[b * 2 + 1], zl[b * D2 + k] * mlt[b * D4 + D2 + k], s);
+    } else {
+      for (int b = 0; b < nr; ++b) s += gx[b * 2 + 1];
+    }
+    hp[e] = s;
+  }
+  if (blockIdx.x == 0 && t == 0) {
+    float mmd = 0.f, dis_term = 0.f;
+    if (a.dis_mode == 0) {          // partial block sums in fixed order, double accumulation (tail_core_kernel's mmd_part branch)
+      const int nm = a.z_global ? a.n_global : B;
+      double s11 = 0.0, s22 = 0.0, s12 = 0.0;
+      for (int p = 0; p < a.mmd_nblk; ++p) { s11 += a.mmd_part[p * 4]; s22 += a.mmd_part[p * 4 + 1]; s12 += a.mmd_part[p * 4 + 2]; }
+      const double b00 = 1.0 / ((double)nm * (nm - 1)), b01 = -1.0 / ((double)nm * nm);
+      mmd = (float)(2.0 * b01 * s12 + b00 * s11 + b00 * s22);
+      dis_term = -a.w_mmd * mmd;
+    }
+    a.terms[1] = mmd; a.terms[2] = l_emo; a.terms[3] = l_cau; a.terms[4] = l_pair; a.terms[5] = kle; a.terms[6] = klc;
+    a.terms[0] = dis_term + a.w_emo * l_emo + a.w_cau * l_cau + a.w_pair * l_pair + kle + klc;
+    a.pair_dead[0] = dead ? 1.f : 0.f;
+  }
+}
+
+// head parameter gradients = the slabs' partials added in slab order
+__global__ __launch_bounds__(TT_THREADS) void tail_head_grads_kernel(TailTiled q, int nslab) {
+  const TailCore& a = q.c;
+  const int D = a.D, D2 = 2 * a.D;
+  const int o_eb = a.EC * D, o_cw = o_eb + a.EC, o_cb = o_cw + D, o_pw = o_cb + 1, o_pb = o_pw + D2, n_hw = o_pb + 1;
+  for (int e = threadIdx.x; e < n_hw; e += TT_THREADS) {
+    float s = 0.f;
+    for (int p = 0; p < nslab; ++p) s += q.hpart[(long)p * n_hw + e];
+    float* dst = e < o_eb ? a.d_emo_w + e : e < o_cw ? a.d_emo_b + (e - o_eb) : e < o_cb ? a.d_cau_w + (e - o_cw) : e < o_pw ? a.d_cau_b
+               : e < o_pb ? a.d_pair_w + (e - o_pw) : a.d_pair_b;
+    *dst = s;
+  }
+}
+
+// The decoder's three passes with the batch walked in tiles of TB rows (TB a multiple of DEC_MAXG; DEC_MAXG sample groups, each
+// a contiguous quarter of the tile).  LDS: z [TB][D2], the chunk's weights, one [TB][DEC_J] tile (two in pass 2).  Passes 1 and 2:
+// grid (chunk, batch tile), partials indexed by row as in decoder_kernel.  Pass 3: one workgroup per chunk walks the tiles in
+// ascending order with dW[j] / db[j] of its sample group in registers, dz_part[chunk][b] written per row; at the end the groups'
+// sums are added in group order (through the weight image, which is free by then).
+template <int PASS, int CD2>
+__global__ __launch_bounds__(DEC_J * DEC_MAXG) void decoder_tiled_kernel(DecArgs a, int TB) {
+  const int D2 = CD2 ? CD2 : a.D2;
+  const int ws = D2 + 1;
+  constexpr int G = DEC_MAXG, NTHR = DEC_J * DEC_MAXG;
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  float* zl = (float*)smem_raw;                       // [TB][D2]
+  float* wl = zl + TB * D2;                           // [DEC_J][D2+1] weights of the chunk
+  float* tile = wl + ((DEC_J * ws + 3) & ~3);         // [TB][DEC_J] per-(sample, entry) values (pass 3: dlogits)
+  float* tile2 = tile + TB * DEC_J;                   // pass 2: second tile
+  const int t = threadIdx.x;
+  const int tj = t & (DEC_J - 1), g = t / DEC_J;
+  const int j0 = blockIdx.x * DEC_J, j = j0 + tj;
+  const bool live = j < a.V;
+  const int nrow = min(DEC_J, a.V - j0);
+  const int Rg = TB / G, lb0 = g * Rg;                // this group's rows of a tile: lb0 .. lb0 + Rg - 1
+  for (int e = t; e < nrow * D2; e += NTHR) { const int r = e / D2, k = e - r * D2; wl[r * ws + k] = a.w[(long)j0 * D2 + e]; }
+  __syncthreads();
+  float wr[CD2 ? CD2 : DEC_MAXD2];
+  _Pragma("unroll") for (int k = 0; k < D2; ++k) wr[k] = live ? wl[tj * ws + k] : 0.f;
+  const float bias = live ? a.b[j] : 0.f;
+  const int lane = t & 63, wv = t >> 6, nwv = NTHR >> 6;
+  if (PASS == 1 || PASS == 2) {
+    const int t0 = blockIdx.y * TB, nb = min(TB, a.B - t0);
+    const int lb1 = min(nb, lb0 + Rg);
+    for (int e = t; e < nb * D2; e += NTHR) zl[e] = a.z[(long)t0 * D2 + e];
+    __syncthreads();
+    if (PASS == 1) {
+      for (int lb = lb0; lb < lb1; ++lb) tile[lb * DEC_J + tj] = live ? dec_logit<CD2>(wr, zl + lb * D2, D2, bias) : -INFINITY;
+      __syncthreads();
+      for (int lb = wv; lb < nb; lb += nwv) {
+        const float x0 = tile[lb * DEC_J + lane], x1 = tile[lb * DEC_J + 64 + lane];
+        const float m = wave_max(fmaxf(x0, x1));
+        const float s2 = wave_sum(expf(x0 - m) + expf(x1 - m));            // exp(-inf - m) = 0 for dead entries
+        if (lane == 0) { a.part[((long)blockIdx.x * a.B + t0 + lb) * 2] = m; a.part[((long)blockIdx.x * a.B + t0 + lb) * 2 + 1] = s2; }
+      }
+    } else {
+      for (int bb = lb0; bb < lb1; bb += 4) {
+        float bw[4];
+        _Pragma("unroll") for (int u = 0; u < 4; ++u) bw[u] = (live && bb + u < lb1) ? a.bow[(long)(t0 + bb + u) * a.V + j] : 0.f;
+        _Pragma("unroll") for (int u = 0; u < 4; ++u) {
+          const int lb = bb + u;
+          if (lb < lb1) {
+            float le = 0.f, dt = 0.f;
+            if (live) {
+              const float lp = dec_logit<CD2>(wr, zl + lb * D2, D2, bias) - a.rowstat[(t0 + lb) * 4] - a.rowstat[(t0 + lb) * 4 + 1];
+              const float p = expf(lp);
+              const float tg = bw[u] * (1.f - a.ls) + a.ls / a.V;
+              le = -(tg * fmaxf(lp, -100.f) + (1.f - tg) * fmaxf(log1pf(-p), -100.f));
+              dt = p * ((p - tg) / fmaxf((1.f - p) * p, 1e-12f));
+            }
+            tile[lb * DEC_J + tj] = le; tile2[lb * DEC_J + tj] = dt;
+          }
+        }
+      }
+      __syncthreads();
+      for (int lb = wv; lb < nb; lb += nwv) {
+        const float le = wave_sum(tile[lb * DEC_J + lane] + tile[lb * DEC_J + 64 + lane]);
+        const float dt = wave_sum(tile2[lb * DEC_J + lane] + tile2[lb * DEC_J + 64 + lane]);
+        if (lane == 0) { a.part[((long)blockIdx.x * a.B + t0 + lb) * 2] = le; a.part[((long)blockIdx.x * a.B + t0 + lb) * 2 + 1] = dt; }
+      }
+    }
+  } else {
+    float dwr[CD2 ? CD2 : DEC_MAXD2];
+    _Pragma("unroll") for (int k = 0; k < D2; ++k) dwr[k] = 0.f;
+    float dbj = 0.f;
+    for (int t0 = 0; t0 < a.B; t0 += TB) {
+      const int nb = min(TB, a.B - t0);
+      const int lb1 = min(nb, lb0 + Rg);
+      __syncthreads();                                  // the previous tile's dz_part sweep has read zl / tile
+      for (int e = t; e < nb * D2; e += NTHR) zl[e] = a.z[(long)t0 * D2 + e];
+      __syncthreads();
+      for (int bb = lb0; bb < lb1; bb += 4) {
+        float bw[4];
+        _Pragma("unroll") for (int u = 0; u < 4; ++u) bw[u] = (live && bb + u < lb1) ? a.bow[(long)(t0 + bb + u) * a.V + j] : 0.f;
+        _Pragma("unroll") for (int u = 0; u < 4; ++u) {
+          const int lb = bb + u;
+          if (lb < lb1) {
+            float gg = 0.f;
+            if (live) {
+              const float lp = dec_logit<CD2>(wr, zl + lb * D2, D2, bias) - a.rowstat[(t0 + lb) * 4] - a.rowstat[(t0 + lb) * 4 + 1];
+              const float p = expf(lp);
+              const float tg = bw[u] * (1.f - a.ls) + a.ls / a.V;
+              const float gp = (p - tg) / fmaxf((1.f - p) * p, 1e-12f);
+              gg = p * (gp - a.rowstat[(t0 + lb) * 4 + 2]) * a.gscale;
+              _Pragma("unroll") for (int k = 0; k < D2; ++k) dwr[k] = fmaf(gg, zl[lb * D2 + k], dwr[k]);
+              dbj += gg;
+            }
+            tile[lb * DEC_J + tj] = gg;
+          }
+        }
+      }
+      __syncthreads();
+      // dz_part[chunk][b][k] = sum_{j in chunk} dlogit[b][j] * W[j][k]
+      for (int e = t; e < nb * D2; e += NTHR) {
+        const int lb = e / D2, k = e - lb * D2;
+        float s = 0.f;
+        for (int jj = 0; jj < nrow; ++jj) s = fmaf(tile[lb * DEC_J + jj], wl[jj * ws + k], s);
+        a.dz_part[((long)blockIdx.x * a.B + t0) * D2 + e] = s;
+      }
+    }
+    for (int p = 1; p < G; ++p) {                       // fixed order: group 0 + group 1 + ...
+      __syncthreads();
+      if (g == p) {
+        _Pragma("unroll") for (int k = 0; k < D2; ++k) wl[tj * ws + k] = dwr[k];
+        tile[tj] = dbj;
+      }
+      __syncthreads();
+      if (g == 0) {
+        _Pragma("unroll") for (int k = 0; k < D2; ++k) dwr[k] += wl[tj * ws + k];
+        dbj += tile[tj];
+      }
+    }
+    if (g == 0 && live) {
+      _Pragma("unroll") for (int k = 0; k < D2; ++k) a.dw[(long)j * D2 + k] = dwr[k];
+      a.db[j] = dbj;
+    }
+  }
+}
+
 }  // namespace carel
 
 using namespace carel;
 
 static size_t align_up(size_t x) { return (x + 63) & ~(size_t)63; }
 constexpr int MMD_MAX_BLOCKS = 1024;          // mmd_global_kernel: 32 rows per block -> up to 16 384 samples per side
+constexpr size_t TAIL_LDS_MAX = 160 * 1024;   // LDS of one CU
 
 struct TailWork {     // carve-up of the caller's f32 workspace
   float* dz_core; float* dlat_direct; float* dlat; float* dpooled; float* dpre; float* part; float* rowstat; float* dz_part;
   float* dcls; float* dgpart; float* pair_dead; float* mmd_part; float* dz_mmd;
+  float* tt_lg; float* tt_spart; float* tt_hpart;      // carel_tail_losses_tiled only; appended, so every earlier offset is where it was
   size_t total;
 };
 static TailWork carve(float* base, int B, int D, int V) {
@@ -662,6 +1023,7 @@ static TailWork carve(float* base, int B, int D, int V) {
   w.dgpart = take((size_t)((TH + DG_CHUNK - 1) / DG_CHUNK) * B * TH);
   w.pair_dead = take(16);
   w.mmd_part = take(4 * MMD_MAX_BLOCKS); w.dz_mmd = take((size_t)B * 2 * D);
+  w.tt_lg = take((size_t)B * 16); w.tt_spart = take((size_t)TT_MAX_SLABS * 8); w.tt_hpart = take((size_t)TT_MAX_SLABS * TT_MAX_NHW);
   w.total = o;
   return w;
 }
@@ -722,31 +1084,57 @@ extern "C" int carel_pair_probs(const void* lat, const void* eps_e, const void* 
   return check_launch("pair_prob_kernel");
 }
 
-// losses + gradients of everything after the latents.  Needs carel_tail_latents() first.
-extern "C" int carel_tail_losses(const carel_tail_args* a, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  int rc = tail_check(a, "carel_tail_losses");
+// ---- the two LDS plans of carel_tail_losses (its batch limit), shared with carel_tail_batch_limit
+// loss kernel (one workgroup): the whole batch's z, dz, dropout multipliers, logits, dlogits and the MMD / HSIC rows (nm per side)
+static size_t tail_core_lds_bytes(int B, int D, int EC, int nm) {
+  const int n_hw = EC * D + EC + D + 1 + 2 * D + 1;
+  return sizeof(float) * (64 + 64 + (size_t)2 * B * 2 * D + (size_t)B * 8 + (size_t)B * 2 + (size_t)B * 4 * D + (size_t)B * 16 +
+                          ((n_hw + 3) & ~3) + ((2 * nm + 3) & ~3) + (size_t)2 * nm * (D | 1) + 2 * (size_t)B);
+}
+// decoder: z + red + weights + tile [B][DEC_J] (+ pass 2: second tile; pass 3: the other groups' dW/db partials)
+struct DecPlan { int G; size_t lds1, lds2, lds3, ldsmax; };
+static DecPlan tail_decoder_plan(int B, int D) {
+  DecPlan p;
+  const size_t lds0 = sizeof(float) * ((size_t)B * 2 * D + 16 + (size_t)DEC_J * (2 * D + 1) + (size_t)B * DEC_J);
+  int G = DEC_MAXG;
+  auto lds3_of = [&](int g) { return lds0 + sizeof(float) * (size_t)(g - 1) * DEC_J * (2 * D + 2); };
+  while (G > 1 && (lds3_of(G) > TAIL_LDS_MAX || (B + G - 1) / G < 4)) G >>= 1;
+  p.G = G; p.lds1 = lds0; p.lds2 = lds0 + sizeof(float) * (size_t)B * DEC_J; p.lds3 = lds3_of(G);
+  p.ldsmax = p.lds2 > p.lds3 ? p.lds2 : p.lds3;
+  return p;
+}
+
+extern "C" int32_t carel_tail_batch_limit(int32_t ec_dim, int32_t e_classes) {
+  if (ec_dim < 1 || ec_dim > 32 || e_classes < 1 || e_classes > 8 || 2 * ec_dim > DEC_MAXD2) return 0;
+  int B = 1;       // both plans grow with the batch: the largest accepted one is the last before the first refusal
+  while (tail_core_lds_bytes(B + 1, ec_dim, e_classes, B + 1) <= TAIL_LDS_MAX && tail_decoder_plan(B + 1, ec_dim).ldsmax <= TAIL_LDS_MAX) ++B;
+  return B >= 2 ? B : 0;
+}
+
+// Argument checks and the loss kernel's arguments, common to carel_tail_losses and carel_tail_losses_tiled (`who` names the caller
+// in the messages).  Nothing is launched here.
+static int tail_losses_prepare(const carel_tail_args* a, const char* who, TailCore& c, TailWork& w) {
+  int rc = tail_check(a, who);
   if (rc) return rc;
   const int B = a->batch, D = a->ec_dim, V = a->bow_dim;
-  if (V < 1) return set_error(CAREL_ERR_SHAPE, "carel_tail_losses: bow_dim must be positive");
-  if (2 * D > DEC_MAXD2) return set_error(CAREL_ERR_SHAPE, "carel_tail_losses: 2*ec_dim must be <= %d", DEC_MAXD2);
-  if (B < 2 && !a->z_global) return set_error(CAREL_ERR_SHAPE, "carel_tail_losses: batch must be >= 2 (MMD divides by n(n-1))");
+  if (V < 1) return set_error(CAREL_ERR_SHAPE, "%s: bow_dim must be positive", who);
+  if (2 * D > DEC_MAXD2) return set_error(CAREL_ERR_SHAPE, "%s: 2*ec_dim must be <= %d", who, DEC_MAXD2);
+  if (B < 2 && !a->z_global) return set_error(CAREL_ERR_SHAPE, "%s: batch must be >= 2 (MMD divides by n(n-1))", who);
   if (!a->emo_w || !a->emo_b || !a->cau_w || !a->cau_b || !a->pair_w || !a->pair_b || !a->dec_w || !a->dec_b ||
       !a->emo_labels || !a->cau_labels || !a->pair_labels || !a->bow || !a->eps_e || !a->eps_c || !a->z || !a->terms ||
       !a->work || !a->d_emo_w || !a->d_emo_b || !a->d_cau_w || !a->d_cau_b || !a->d_pair_w || !a->d_pair_b || !a->d_dec_w ||
       !a->d_dec_b)
-    return set_error(CAREL_ERR_ARG, "carel_tail_losses: null tensor");
-  TailWork w = carve((float*)a->work, B, D, V);
-  TailCore c;
+    return set_error(CAREL_ERR_ARG, "%s: null tensor", who);
+  w = carve((float*)a->work, B, D, V);
   c.B = B; c.D = D; c.EC = a->e_classes; c.lat = (const float*)a->lat; c.eps_e = (const float*)a->eps_e; c.eps_c = (const float*)a->eps_c;
   c.emo_w = (const float*)a->emo_w; c.emo_b = (const float*)a->emo_b; c.cau_w = (const float*)a->cau_w; c.cau_b = (const float*)a->cau_b;
   c.pair_w = (const float*)a->pair_w; c.pair_b = (const float*)a->pair_b;
   c.emo_labels = (const long*)a->emo_labels; c.cau_labels = (const float*)a->cau_labels; c.pair_labels = (const float*)a->pair_labels;
   c.w_mmd = a->w_mmd; c.w_emo = a->w_emo; c.w_cau = a->w_cau; c.w_pair = a->w_pair; c.kl_w = a->kl_weight; c.ls = a->label_smoothing;
   c.dis_mode = a->dis_mode; c.emo_bce = a->emo_bce;
-  if (c.dis_mode < 0 || c.dis_mode > 2) return set_error(CAREL_ERR_ARG, "carel_tail_losses: dis_mode must be 0 (MMD), 1 (HSIC) or 2 (none)");
-  if (c.emo_bce && a->e_classes != 1) return set_error(CAREL_ERR_ARG, "carel_tail_losses: the BCE emotion head has exactly one logit");
-  if (c.dis_mode == 1 && a->z_global) return set_error(CAREL_ERR_ARG, "carel_tail_losses: HSIC has no global-batch mode");
+  if (c.dis_mode < 0 || c.dis_mode > 2) return set_error(CAREL_ERR_ARG, "%s: dis_mode must be 0 (MMD), 1 (HSIC) or 2 (none)", who);
+  if (c.emo_bce && a->e_classes != 1) return set_error(CAREL_ERR_ARG, "%s: the BCE emotion head has exactly one logit", who);
+  if (c.dis_mode == 1 && a->z_global) return set_error(CAREL_ERR_ARG, "%s: HSIC has no global-batch mode", who);
   c.d_emo = make_dropout(a->drop_seed, 100u, a->drop_p, a->drop_row_offset * (uint32_t)D);
   c.d_cau = make_dropout(a->drop_seed, 101u, a->drop_p, a->drop_row_offset * (uint32_t)D);
   c.d_pair = make_dropout(a->drop_seed, 102u, a->drop_p, a->drop_row_offset * (uint32_t)(2 * D));
@@ -754,36 +1142,42 @@ extern "C" int carel_tail_losses(const carel_tail_args* a, void* stream_) {
   c.label_sum_override = (const float*)a->global_label_sum; c.n_override = (float)a->global_n;
   c.label_sum_ranks = a->global_label_ranks > 1 ? a->global_label_ranks : 1;
   if (c.label_sum_ranks > 1 && a->global_rank_stride <= 0)
-    return set_error(CAREL_ERR_ARG, "carel_tail_losses: global_label_ranks > 1 needs global_rank_stride");
+    return set_error(CAREL_ERR_ARG, "%s: global_label_ranks > 1 needs global_rank_stride", who);
   c.z_global = (const float*)a->z_global; c.n_global = a->global_n; c.row_offset = a->global_row_offset;
   c.rank_stride = a->global_rank_stride > 0 ? a->global_rank_stride : B * 2 * D;
   if (c.z_global && a->global_rank_stride > 0 && (a->global_rank_stride < B * 2 * D || c.n_global % B))
-    return set_error(CAREL_ERR_ARG, "carel_tail_losses: global_rank_stride needs global_n to be a multiple of batch and stride >= batch*2*ec_dim");
+    return set_error(CAREL_ERR_ARG, "%s: global_rank_stride needs global_n to be a multiple of batch and stride >= batch*2*ec_dim", who);
   c.mmd_grad_scale = a->mmd_grad_scale > 0.f ? a->mmd_grad_scale : 1.f;
   if (c.z_global && (c.n_global < 2 || c.row_offset < 0 || c.row_offset + B > c.n_global))
-    return set_error(CAREL_ERR_ARG, "carel_tail_losses: inconsistent global batch description");
+    return set_error(CAREL_ERR_ARG, "%s: inconsistent global batch description", who);
   c.z = (float*)a->z; c.terms = (float*)a->terms; c.dz = w.dz_core; c.dlat_direct = w.dlat_direct;
   c.d_emo_w = (float*)a->d_emo_w; c.d_emo_b = (float*)a->d_emo_b; c.d_cau_w = (float*)a->d_cau_w; c.d_cau_b = (float*)a->d_cau_b;
   c.d_pair_w = (float*)a->d_pair_w; c.d_pair_b = (float*)a->d_pair_b; c.pair_dead = w.pair_dead;
+  c.mmd_part = nullptr; c.mmd_nblk = 0; c.dz_mmd = nullptr; c.prof = nullptr;
+  return CAREL_OK;
+}
+
+// losses + gradients of everything after the latents.  Needs carel_tail_latents() first.
+extern "C" int carel_tail_losses(const carel_tail_args* a, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  TailCore c; TailWork w;
+  int rc = tail_losses_prepare(a, "carel_tail_losses", c, w);
+  if (rc) return rc;
+  const int B = a->batch, D = a->ec_dim, V = a->bow_dim;
   const int nm = (c.z_global && c.dis_mode != 0) ? c.n_global : B;        // the global-batch MMD runs in its own kernel
-  const int n_hw = a->e_classes * D + a->e_classes + D + 1 + 2 * D + 1;
-  const size_t lds = sizeof(float) * (64 + 64 + (size_t)2 * B * 2 * D + (size_t)B * 8 + (size_t)B * 2 + (size_t)B * 4 * D + (size_t)B * 16 +
-                                      ((n_hw + 3) & ~3) + ((2 * nm + 3) & ~3) + (size_t)2 * nm * (D | 1) + 2 * (size_t)B);
-  if (lds > 160 * 1024) return set_error(CAREL_ERR_SHAPE, "carel_tail_losses: batch too large for the single-workgroup tail (%zu B LDS)", lds);
+  const size_t lds = tail_core_lds_bytes(B, D, a->e_classes, nm);
+  if (lds > TAIL_LDS_MAX) return set_error(CAREL_ERR_SHAPE, "carel_tail_losses: batch too large for the single-workgroup tail (%zu B LDS)", lds);
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute((const void*)tail_core_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return set_error(CAREL_ERR_HIP, "carel_tail_losses: hipFuncSetAttribute: %s", hipGetErrorString(e));
   }
-  // The decoder's launch plan.  LDS: z + red + weights + tile [B][DEC_J] (+ pass 2: second tile; pass 3: the other groups' dW/db partials).
-  // Together with the check above this is the batch limit of the call: both kernels keep the whole batch in the 160 KB LDS of one CU.
+  // The decoder's launch plan.  Together with the check above this is the batch limit of the call (carel_tail_batch_limit): both
+  // kernels keep the whole batch in the 160 KB LDS of one CU.
   const int chunks = (V + DEC_J - 1) / DEC_J;
-  const size_t lds0 = sizeof(float) * ((size_t)B * 2 * D + 16 + (size_t)DEC_J * (2 * D + 1) + (size_t)B * DEC_J);
-  int G = DEC_MAXG;
-  auto lds3_of = [&](int g) { return lds0 + sizeof(float) * (size_t)(g - 1) * DEC_J * (2 * D + 2); };
-  while (G > 1 && (lds3_of(G) > 160 * 1024 || (B + G - 1) / G < 4)) G >>= 1;
-  const size_t lds1 = lds0, lds2 = lds0 + sizeof(float) * (size_t)B * DEC_J, lds3 = lds3_of(G);
-  const size_t ldsmax = lds2 > lds3 ? lds2 : lds3;
-  if (ldsmax > 160 * 1024) return set_error(CAREL_ERR_SHAPE, "carel_tail_losses: batch too large for the decoder kernel (%zu B LDS)", ldsmax);
+  const DecPlan dp = tail_decoder_plan(B, D);
+  const int G = dp.G;
+  const size_t lds1 = dp.lds1, lds2 = dp.lds2, lds3 = dp.lds3, ldsmax = dp.ldsmax;
+  if (ldsmax > TAIL_LDS_MAX) return set_error(CAREL_ERR_SHAPE, "carel_tail_losses: batch too large for the decoder kernel (%zu B LDS)", ldsmax);
   if (ldsmax > 64 * 1024) {
     hipError_t e = hipSuccess;
     const void* fns[6] = {(const void*)decoder_kernel<1, 48>, (const void*)decoder_kernel<2, 48>, (const void*)decoder_kernel<3, 48>,
@@ -856,6 +1250,76 @@ extern "C" int carel_tail_losses(const carel_tail_args* a, void* stream_) {
   hipLaunchKernelGGL(reduce_parts16_kernel, dim3((B * 2 * D + 15) / 16), dim3(256), 0, stream, (const float*)w.dz_part, w.dz_part, B * 2 * D, chunks);
   if (tev && hipStreamWaitEvent(stream, tev->join, 0) != hipSuccess) return join_on_error(set_error(CAREL_ERR_HIP, "carel_tail_losses: event join failed"));
   hipLaunchKernelGGL(decoder_total_kernel, dim3(1), dim3(256), 0, stream, (const float*)w.rowstat, B, d.gscale, (float*)a->terms);   // reads terms[0] of the loss kernel
+  hipLaunchKernelGGL(tail_dlat_kernel, dim3((B * 2 * D + 255) / 256), dim3(256), 0, stream, (const float*)w.dz_core, (const float*)w.dz_part,
+                     1, (const float*)w.dlat_direct, (const float*)a->lat, (const float*)a->eps_e, (const float*)a->eps_c, B, D, 1.0f, w.dlat);
+  return check_launch("tail_dlat_kernel");
+}
+
+// The batch-tiled form of carel_tail_losses: same contract, same outputs, same workspace carve, same dropout streams, the same
+// data-parallel hooks; 2 <= batch <= 1024 (1 with z_global), MMD or no statistic.  LDS per workgroup does not depend on the batch
+// and stays below 64 KB.  Everything runs on the caller's stream (nothing here is a one-CU kernel worth hiding), so the call is
+// re-entrant.  Every check comes before the first launch.
+extern "C" int carel_tail_losses_tiled(const carel_tail_args* a, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const char* who = "carel_tail_losses_tiled";
+  if (!a) return set_error(CAREL_ERR_ARG, "%s: null args", who);
+  if (a->batch > TT_MAX_B) return set_error(CAREL_ERR_SHAPE, "%s: batch must be <= %d; got %d", who, TT_MAX_B, a->batch);
+  TailTiled q; TailWork w;
+  TailCore& c = q.c;
+  int rc = tail_losses_prepare(a, who, c, w);
+  if (rc) return rc;
+  const int B = a->batch, D = a->ec_dim, V = a->bow_dim;
+  if (c.dis_mode == 1)
+    return set_error(CAREL_ERR_SHAPE, "%s: HSIC (dis_mode 1) keeps the single-workgroup limit of carel_tail_losses: batch <= %d at ec_dim %d, "
+                     "e_classes %d; got %d", who, (int)carel_tail_batch_limit(D, a->e_classes), D, a->e_classes, B);
+  const int nm = c.z_global ? c.n_global : B;        // samples per side of the MMD
+  const int nblk = (2 * nm + 31) / 32;
+  if (c.dis_mode == 0 && nblk > MMD_MAX_BLOCKS) return set_error(CAREL_ERR_SHAPE, "%s: global batch too large for the MMD partial buffer", who);
+  const int nslab = (B + TT_R - 1) / TT_R;
+  const int n_hw = a->e_classes * D + a->e_classes + D + 1 + 2 * D + 1;
+  const size_t lds_h = sizeof(float) * (64 + (size_t)TT_R * (2 * D + 4 * D + 16 + 8 + 2) + ((n_hw + 3) & ~3));
+  const int D2 = 2 * D, chunks = (V + DEC_J - 1) / DEC_J;
+  auto dec_lds = [&](int tb, int tiles) { return sizeof(float) * ((size_t)tb * D2 + ((DEC_J * (D2 + 1) + 3) & ~3) + (size_t)tiles * tb * DEC_J); };
+  const int TB = dec_lds(32, 2) <= 64 * 1024 ? 32 : 16;
+  if (lds_h > 64 * 1024 || dec_lds(TB, 2) > 64 * 1024 || nslab > TT_MAX_SLABS || n_hw > TT_MAX_NHW)
+    return set_error(CAREL_ERR_SHAPE, "%s: internal tile plan does not fit (ec_dim %d, e_classes %d)", who, D, a->e_classes);
+  const int ntile = (B + TB - 1) / TB;
+  q.lg = w.tt_lg; q.spart = w.tt_spart; q.hpart = w.tt_hpart;
+
+  hipLaunchKernelGGL(sample_z_kernel, dim3((B * 2 * D + 255) / 256), dim3(256), 0, stream, c.lat, c.eps_e, c.eps_c, B, D, c.z);
+  if (c.dis_mode == 0) {
+    MmdGlobalArgs g;
+    g.zg = c.z_global ? c.z_global : (const float*)c.z; g.n = nm; g.B = B; g.D = D;
+    g.rank_stride = c.z_global ? c.rank_stride : B * 2 * D; g.row_offset = c.z_global ? c.row_offset : 0;
+    g.alpha = c.alpha; g.eps = c.mmd_eps; g.gscale = -c.w_mmd * c.mmd_grad_scale; g.part = w.mmd_part; g.dz = w.dz_mmd;
+    if (D == 24) hipLaunchKernelGGL(mmd_global_kernel<24>, dim3(nblk), dim3(256), 0, stream, g);
+    else hipLaunchKernelGGL(mmd_global_kernel<32>, dim3(nblk), dim3(256), 0, stream, g);
+    if ((rc = check_launch("mmd_global_kernel"))) return rc;
+    c.mmd_part = w.mmd_part; c.mmd_nblk = nblk; c.dz_mmd = w.dz_mmd;
+  }
+  hipLaunchKernelGGL(tail_heads_kernel<1>, dim3(nslab), dim3(TT_THREADS), lds_h, stream, q);
+  hipLaunchKernelGGL(tail_heads_kernel<2>, dim3(nslab), dim3(TT_THREADS), lds_h, stream, q);
+  hipLaunchKernelGGL(tail_head_grads_kernel, dim3(1), dim3(TT_THREADS), 0, stream, q, nslab);
+  if ((rc = check_launch("tail_heads_kernel"))) return rc;
+
+  DecArgs d;
+  d.B = B; d.D2 = D2; d.V = V; d.z = (const float*)a->z; d.w = (const float*)a->dec_w; d.b = (const float*)a->dec_b;
+  d.bow = (const float*)a->bow; d.ls = a->label_smoothing; d.part = w.part; d.rowstat = w.rowstat; d.dz_part = w.dz_part;
+  d.dw = (float*)a->d_dec_w; d.db = (float*)a->d_dec_b; d.gscale = 1.0f / ((float)B * (float)V);
+#define DEC_TILED_LAUNCH(PASS, GRID, LDS)                                                                                         \
+  do {                                                                                                                         \
+    if (D2 == 48) hipLaunchKernelGGL((decoder_tiled_kernel<PASS, 48>), GRID, dim3(DEC_J * DEC_MAXG), LDS, stream, d, TB);          \
+    else hipLaunchKernelGGL((decoder_tiled_kernel<PASS, 0>), GRID, dim3(DEC_J * DEC_MAXG), LDS, stream, d, TB);                    \
+  } while (0)
+  DEC_TILED_LAUNCH(1, dim3(chunks, ntile), dec_lds(TB, 1));
+  hipLaunchKernelGGL(decoder_combine_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, (const float*)w.part, chunks, B, 1, w.rowstat);
+  DEC_TILED_LAUNCH(2, dim3(chunks, ntile), dec_lds(TB, 2));
+  hipLaunchKernelGGL(decoder_combine_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, (const float*)w.part, chunks, B, 2, w.rowstat);
+  DEC_TILED_LAUNCH(3, dim3(chunks), dec_lds(TB, 1));
+#undef DEC_TILED_LAUNCH
+  if ((rc = check_launch("decoder kernels (tiled)"))) return rc;
+  hipLaunchKernelGGL(reduce_parts16_kernel, dim3((B * 2 * D + 15) / 16), dim3(256), 0, stream, (const float*)w.dz_part, w.dz_part, B * 2 * D, chunks);
+  hipLaunchKernelGGL(decoder_total_kernel, dim3(1), dim3(256), 0, stream, (const float*)w.rowstat, B, d.gscale, (float*)a->terms);
   hipLaunchKernelGGL(tail_dlat_kernel, dim3((B * 2 * D + 255) / 256), dim3(256), 0, stream, (const float*)w.dz_core, (const float*)w.dz_part,
                      1, (const float*)w.dlat_direct, (const float*)a->lat, (const float*)a->eps_e, (const float*)a->eps_c, B, D, 1.0f, w.dlat);
   return check_launch("tail_dlat_kernel");

@@ -953,6 +953,7 @@ class DrlClassifier(nn.Module):
             c.labels["emo_f"] = emotion_labels.to(dev, f32).reshape(-1).contiguous()     # the adversaries score float labels (:83, :133)
             if c.labels["emo_f"].numel() != B or c.labels["cau"].numel() != B:
                 raise L.CarelError("emotion_labels and cause_labels must hold one value per pair")
+        self._check_tail_batch(B)
         key = ("tail", B, S)
         buf = self._ws.get(key)
         if buf is None:
@@ -962,6 +963,19 @@ class DrlClassifier(nn.Module):
         if self._dp is not None:
             self._dp.prepare(c)
         return c
+
+    def _check_tail_batch(self, B):
+        """The combinations the loss step refuses, raised when the batch is known and before the encoder runs: above the
+        single-workgroup limit of carel_tail_losses the batch-tiled form takes over (ops.tail_losses), which has MMD or no statistic
+        (vi and gan add theirs beside it, within their own kernels' limits) and at most 1024 rows."""
+        limit = ops.tail_batch_limit(self.opt.ec_dim, self.opt.e_num_class)
+        if B <= limit:
+            return
+        if getattr(self.opt, "disentangle", "mmd") == "hsic":
+            raise L.CarelError("opt.disentangle == 'hsic' keeps the single-workgroup tail: batch <= %d per GPU at ec_dim %d; got %d "
+                               "(the other disentanglers train up to 1024 per GPU)" % (limit, self.opt.ec_dim, B))
+        if B > 1024:
+            raise L.CarelError("the loss step takes at most 1024 pairs per GPU (--batch_size); got %d" % B)
 
     def _tail_weights(self):
         keys = ["encoder.pooler.dense.weight", "encoder.pooler.dense.bias", "decoder.weight", "decoder.bias"]

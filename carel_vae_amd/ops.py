@@ -206,8 +206,22 @@ def tail_latents(a):
     L.check(L.load().carel_tail_latents(C.byref(a), L.current_stream()), "carel_tail_latents")
 
 
+def tail_batch_limit(ec_dim, e_classes):
+    """The largest batch carel_tail_losses (the single-workgroup form) accepts; above it tail_losses takes the batch-tiled form."""
+    return int(L.load().carel_tail_batch_limit(int(ec_dim), int(e_classes)))
+
+
+def tail_losses_tiled(a):
+    """carel_tail_losses_tiled: the batch-tiled loss step, 2 <= batch <= 1024 (MMD or no statistic)."""
+    L.check(L.load().carel_tail_losses_tiled(C.byref(a), L.current_stream()), "carel_tail_losses_tiled")
+
+
 def tail_losses(a):
-    L.check(L.load().carel_tail_losses(C.byref(a), L.current_stream()), "carel_tail_losses")
+    """The loss step: carel_tail_losses up to its batch limit (unchanged kernels, launches and bits), the batch-tiled form above it."""
+    if a.batch <= tail_batch_limit(a.ec_dim, a.e_classes):
+        L.check(L.load().carel_tail_losses(C.byref(a), L.current_stream()), "carel_tail_losses")
+    else:
+        tail_losses_tiled(a)
 
 
 def tail_backward(a, grad_out=None, dz_extra=None):

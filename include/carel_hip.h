@@ -415,7 +415,24 @@ int carel_encoder_backward_embeddings(const carel_encoder_args* args, void* stre
  *       24   |        114           |        149
  *       32   |        101           |        115
  * The smaller figure holds (any bow_dim).  A larger batch (and batch < 2 without z_global) returns CAREL_ERR_SHAPE before
- * anything is launched: no output is touched and no work is left on the side stream.
+ * anything is launched: no output is touched and no work is left on the side stream.  The table belongs to carel_tail_losses
+ * alone; carel_tail_batch_limit(ec_dim, e_classes) computes it from the same two LDS plans.
+ *
+ *   carel_tail_losses_tiled : the batch-tiled form of carel_tail_losses for batches beyond that limit.  Same contract (needs
+ *                        carel_tail_latents first), same outputs (z, terms[0..8], the six classifier gradients, the decoder
+ *                        gradients, the pair_dead flag, d(loss)/d lat in `work` for carel_tail_backward[_dz]), same workspace,
+ *                        same dropout streams from the same element indices, same data-parallel hooks.  The heads / losses / KL
+ *                        run over slabs of 64 rows in two phases (the pair label sum, the divisor of every mean and the "dead"
+ *                        decision on the batch-mean pair loss are those of the whole batch), the MMD in the row-blocked kernel
+ *                        of the global-batch path, the decoder passes over tiles of 32 (ec_dim <= 25) or 16 rows; LDS per
+ *                        workgroup is below 64 KB whatever the batch.  No atomics: every sum has an order fixed by indices, a
+ *                        repeated call gives the same bits (which differ from carel_tail_losses' in the last places, the sums
+ *                        being ordered differently; z is bit-identical).
+ *                        Limits: 2 <= batch <= 1024 (1 with z_global; small batches are accepted), ec_dim <= 32, e_classes <= 8,
+ *                        both emotion heads, dis_mode 0 (MMD) and 2 (none).  dis_mode 1 (HSIC) keeps the single-workgroup
+ *                        limit: CAREL_ERR_SHAPE, the message names the limit.  Every check comes before the first launch: a
+ *                        refused call touches no output and leaves nothing enqueued.  Everything runs on `stream` (`serial` is
+ *                        ignored, the side stream is not used), so the call is re-entrant.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct carel_tail_args {
   int32_t batch, seq_len, hidden, ec_dim, e_classes, bow_dim;
@@ -480,6 +497,9 @@ int64_t carel_tail_workspace_floats(int32_t batch, int32_t ec_dim, int32_t bow_d
  * all-gather z before carel_tail_losses, which recomputes the same z) */
 int carel_tail_latents(const carel_tail_args* args, void* stream);
 int carel_tail_losses(const carel_tail_args* args, void* stream);
+/* HOST function: the largest batch carel_tail_losses accepts at this width (without z_global), 0 for widths the tail refuses */
+int32_t carel_tail_batch_limit(int32_t ec_dim, int32_t e_classes);
+int carel_tail_losses_tiled(const carel_tail_args* args, void* stream);
 /* Measurement aid: while a device buffer of 16 int64 is registered, the fused loss kernel of carel_tail_losses writes
  * 100 MHz time stamps at its phase boundaries into it (NULL switches it off). */
 int carel_tail_profile(void* dev_i64_x16);
