@@ -208,6 +208,11 @@ class EnTailArgs(C.Structure):
                 ("dx_last_f32", C.c_void_p)]
 
 
+class EnBowArgs(C.Structure):
+    """carel_en_bow_args (include/carel_hip.h)."""
+    _fields_ = [("work", C.c_void_p)]
+
+
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
 EPI_BIAS_BF16, EPI_BIAS_GELU, EPI_BIAS_DROP_RESID, EPI_DGELU_BF16, EPI_ADD_F32, EPI_SLAB_F32, EPI_BIAS_GELU_DG, EPI_MUL_BF16 = range(8)
 
@@ -300,6 +305,8 @@ SIGNATURES = {
     "carel_en_tail_latents": (C.c_int, [C.POINTER(EnTailArgs), C.c_void_p]),
     "carel_en_tail_losses": (C.c_int, [C.POINTER(EnTailArgs), C.c_void_p]),
     "carel_en_tail_backward": (C.c_int, [C.POINTER(EnTailArgs), C.c_void_p, C.c_void_p]),
+    "carel_en_tail_bow_workspace_floats": (C.c_int64, [C.c_int32] * 3),
+    "carel_en_tail_losses_bow": (C.c_int, [C.POINTER(EnTailArgs), C.POINTER(EnBowArgs), C.c_void_p]),
     "carel_en_pair_logits": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "carel_host_pack_batch": (C.c_int, [C.POINTER(HostPackArgs)]),
     "carel_bow_expand": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),

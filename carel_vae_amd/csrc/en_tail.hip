@@ -9,6 +9,9 @@
 // The vocabulary-wide heads (K = 24, 24, 384, 432 inputs -> V outputs) go through an fp32 tiled GEMM: logits [B, V]
 // are written once, a row kernel turns them into d(loss)/d(logits) in place, and two more GEMMs give the weight and
 // input gradients.  HBM-bound on the [V, K] weight images (41 MB for the decoder at V = 23 771).
+// carel_en_tail_losses_bow is the same tail with the element-weighted content losses of drl_classifier_bow_loss.py (:245-257): one more
+// GEMM and an element-wise pass write the weights sigmoid(content_classifier(dropout(z_content))) once, and the row kernel of the two
+// content-discriminator heads and of the content classifier takes them through a compile-time weight mode.
 #include "carel_hip_internal.h"
 #include "rowvec_device.h"
 
@@ -119,8 +122,19 @@ __device__ __forceinline__ float br_log1m(float p) {
   return __logf(1.f - p);
 }
 constexpr int BR_CHUNK = 2048, BR_THREADS = 256, BR_NPT = BR_CHUNK / BR_THREADS;
-template <int ENT, int PASS>
-__global__ __launch_bounds__(BR_THREADS) void bow_row_kernel(BowRowArgs a, float* __restrict__ part, float* __restrict__ part2, int chunks) {
+// Element weights of the BCE part (drl_classifier_bow_loss.py :438-448, :537-550: nn.BCELoss(weight = ...)), a compile-time mode:
+//   BW_NONE: none (the instantiations of carel_en_tail_losses, unchanged);  BW_W: omega = w;  BW_ONE_MINUS: omega = 1 - w
+// with w [B, V] a constant of the row passes (detached in the reference).  rowstat[b][0] = sum_j omega_j bce_j (the logs clamped before the
+// multiply, as nn.BCELoss does), dL_j = p_j (omega_j g_j - sum_k p_k omega_k g_k) * s_bce; the entropy part is not weighted.
+enum { BW_NONE = 0, BW_W = 1, BW_ONE_MINUS = 2 };
+struct BowRowArgsW : BowRowArgs { const float* wgt; };
+template <int WM> struct BowRowArgsOf { typedef BowRowArgsW type; };
+template <> struct BowRowArgsOf<BW_NONE> { typedef BowRowArgs type; };
+__device__ __forceinline__ const float* br_wgt(const BowRowArgs&) { return nullptr; }
+__device__ __forceinline__ const float* br_wgt(const BowRowArgsW& a) { return a.wgt; }
+template <int ENT, int PASS, int WM = BW_NONE>
+__global__ __launch_bounds__(BR_THREADS) void bow_row_kernel(typename BowRowArgsOf<WM>::type a, float* __restrict__ part, float* __restrict__ part2,
+                                                             int chunks) {
   __shared__ float red[16];
   const int c = blockIdx.x, b = blockIdx.y, t = threadIdx.x, V = a.V;
   float* L = a.L + (long)b * V;
@@ -150,14 +164,31 @@ __global__ __launch_bounds__(BR_THREADS) void bow_row_kernel(BowRowArgs a, float
   float tg[BR_NPT];
 #pragma unroll
   for (int i = 0; i < BR_NPT; ++i) { const int j = j0 + t + i * BR_THREADS; tg[i] = j < V ? bw[j] * t1 + t0 : 0.f; }
+  float om[BR_NPT];
+  if (WM != BW_NONE) {
+    const float* wr = br_wgt(a) + (long)b * V;
+#pragma unroll
+    for (int i = 0; i < BR_NPT; ++i) {
+      const int j = j0 + t + i * BR_THREADS;
+      const float wv = j < V ? wr[j] : 0.f;
+      om[i] = WM == BW_W ? wv : 1.f - wv;
+    }
+  }
   if (PASS == 2) {
     float le = 0.f, db = 0.f, en = 0.f, de = 0.f;
 #pragma unroll
     for (int i = 0; i < BR_NPT; ++i) {
       if (j0 + t + i * BR_THREADS < V) {
         const float lp = x[i] - lse, p = __expf(lp);
-        le += -(tg[i] * fmaxf(lp, -100.f) + (1.f - tg[i]) * fmaxf(br_log1m(p), -100.f));
-        db += p * ((p - tg[i]) * __frcp_rn(fmaxf((1.f - p) * p, 1e-12f)));
+        if (WM == BW_NONE) {
+          le += -(tg[i] * fmaxf(lp, -100.f) + (1.f - tg[i]) * fmaxf(br_log1m(p), -100.f));
+          db += p * ((p - tg[i]) * __frcp_rn(fmaxf((1.f - p) * p, 1e-12f)));
+        } else {      // the operations the two lines above compile to (which products are fused), spelled out, with omega multiplied in
+                      // before the sums: omega = 1/2 everywhere gives exactly half of the unweighted statistics
+          const float ll = fmaf(tg[i], fmaxf(lp, -100.f), __fmul_rn(1.f - tg[i], fmaxf(br_log1m(p), -100.f)));      // = -bce_j
+          le = fmaf(om[i], -ll, le);
+          db = fmaf(p, __fmul_rn(om[i], __fmul_rn(p - tg[i], __frcp_rn(fmaxf((1.f - p) * p, 1e-12f)))), db);
+        }
         if (ENT) { const float lg = __logf(p + a.eps); en += p * lg; de += p * (lg + p * __frcp_rn(p + a.eps)); }
       }
     }
@@ -178,7 +209,9 @@ __global__ __launch_bounds__(BR_THREADS) void bow_row_kernel(BowRowArgs a, float
       const float p = __expf(x[i] - lse);
       const float gp = (p - tg[i]) * __frcp_rn(fmaxf((1.f - p) * p, 1e-12f));
       if (ENT) { const float lg = __logf(p + a.eps); a.L2[(long)b * V + j] = p * ((lg + p * __frcp_rn(p + a.eps)) - de) * a.s_ent; }
-      L[j] = p * (gp - db) * a.s_bce;
+      if (WM == BW_NONE) L[j] = p * (gp - db) * a.s_bce;
+      else      // one rounding for omega g - db, as the unweighted line compiles to (a fused multiply-add): omega = 1/2 gives half its bits
+        L[j] = p * fmaf(om[i] * (p - tg[i]), __frcp_rn(fmaxf((1.f - p) * p, 1e-12f)), -db) * a.s_bce;
     }
   }
   if (c == 0 && t == 0) { a.rowstat[b * 2] = le; a.rowstat[b * 2 + 1] = en; }
@@ -199,6 +232,23 @@ __global__ __launch_bounds__(256) void colsum_rows_kernel(const float* __restric
   }
   for (; b < B; ++b) s += X[(long)b * V + j];
   out[j] = accumulate ? out[j] + s : s;
+}
+
+// xw[b][k] = z[b][2D + k] * mask: the content sample under its own dropout draw (site 120), input of the weight matrix
+__global__ __launch_bounds__(256) void en_bow_copy_kernel(const float* __restrict__ z, int B, int D, int Cd, Dropout d, float* __restrict__ xw) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= B * Cd) return;
+  const int b = e / Cd, k = e - b * Cd;
+  xw[e] = z[(long)b * (2 * D + Cd) + 2 * D + k] * dropout_mult(d, (uint32_t)e);
+}
+
+// w = sigmoid(w) in place, once per element: the row passes of three heads read it instead of evaluating it nine times.  Evaluated in
+// fp64 and rounded once (B * V values per step: nothing next to the row passes), so the stored weight is the fp32 number nearest to the
+// sigmoid of its logit and 1 - w in the row kernel adds at most one more rounding.
+__global__ __launch_bounds__(256) void sigmoid_inplace_kernel(float* __restrict__ w, long n) {
+  long i = (long)blockIdx.x * 256 + threadIdx.x;
+  const long stride = (long)gridDim.x * 256;
+  for (; i < n; i += stride) w[i] = (float)(1.0 / (1.0 + exp(-(double)w[i])));
 }
 
 // ------------------------------------------------------------------------------------------
@@ -561,6 +611,7 @@ struct BowHead {
   float* gew; float* geb; int acc_ge;          // gradient of the entropy part (ent only)
   float* dx;                                   // [B, K] or null
   float* rowstat;
+  int wmode = BW_NONE; const float* wgt = nullptr;      // element weights of the BCE part ([B, V], carel_en_tail_losses_bow)
 };
 static int bow_head(const carel_en_tail_args* a, const EnWork& w, const BowHead& h, hipStream_t stream) {
   const int B = a->batch, V = a->bow_dim;
@@ -575,7 +626,17 @@ static int bow_head(const carel_en_tail_args* a, const EnWork& w, const BowHead&
     if (h.ent) hipLaunchKernelGGL((bow_row_kernel<1, PASS>), rg, dim3(BR_THREADS), 0, stream, r, w.rowpart, w.rowpart2, chunks);  \
     else hipLaunchKernelGGL((bow_row_kernel<0, PASS>), rg, dim3(BR_THREADS), 0, stream, r, w.rowpart, w.rowpart2, chunks);        \
   } while (0)
-  BOW_ROW(1); BOW_ROW(2); BOW_ROW(3);
+#define BOW_ROW_W(ENT, PASS, WM) hipLaunchKernelGGL((bow_row_kernel<ENT, PASS, WM>), rg, dim3(BR_THREADS), 0, stream, rw, w.rowpart, w.rowpart2, chunks)
+  if (h.wmode == BW_NONE) {
+    BOW_ROW(1); BOW_ROW(2); BOW_ROW(3);
+  } else {          // pass 1 (maximum, sum of exp) does not see the weights
+    BowRowArgsW rw; (BowRowArgs&)rw = r; rw.wgt = h.wgt;
+    BOW_ROW(1);
+    if (h.ent && h.wmode == BW_ONE_MINUS) { BOW_ROW_W(1, 2, BW_ONE_MINUS); BOW_ROW_W(1, 3, BW_ONE_MINUS); }      // content discriminator
+    else if (!h.ent && h.wmode == BW_W) { BOW_ROW_W(0, 2, BW_W); BOW_ROW_W(0, 3, BW_W); }                         // content classifier
+    else return set_error(CAREL_ERR_ARG, "bow head: no such weighted instantiation");
+  }
+#undef BOW_ROW_W
 #undef BOW_ROW
   if ((rc = check_launch("bow_row_kernel"))) return rc;
   // dW[j][k] = sum_b dL[b][j] x[b][k]
@@ -596,22 +657,38 @@ static int bow_head(const carel_en_tail_args* a, const EnWork& w, const BowHead&
   return check_launch("bow head");
 }
 
-extern "C" int carel_en_tail_losses(const carel_en_tail_args* a, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  int rc = en_check(a, "carel_en_tail_losses");
+// scratch of carel_en_tail_losses_bow: the content sample under dropout site 120 [B, con_dim], then the weight matrix [B, V]
+struct EnBowWork { float* xw; float* conw; size_t total; };
+static EnBowWork en_bow_carve(float* base, int B, int Cd, int V) {
+  EnBowWork w; size_t o = 0;
+  auto take = [&](size_t n) { float* p = base ? base + o : nullptr; o += en_align(n); return p; };
+  w.xw = take((size_t)B * Cd); w.conw = take((size_t)B * V);
+  w.total = o;
+  return w;
+}
+
+extern "C" int64_t carel_en_tail_bow_workspace_floats(int32_t batch, int32_t con_dim, int32_t bow_dim) {
+  if (batch < 1 || con_dim < 1 || bow_dim < 1) return 0;
+  return (int64_t)en_bow_carve(nullptr, batch, con_dim, bow_dim).total;
+}
+
+// bw == nullptr: carel_en_tail_losses;  otherwise the element-weighted content losses of carel_en_tail_losses_bow
+static int en_tail_losses(const carel_en_tail_args* a, const carel_en_bow_args* bw, const char* who, hipStream_t stream) {
+  int rc = en_check(a, who);
   if (rc) return rc;
   const int B = a->batch, D = a->ec_dim, Cd = a->con_dim, V = a->bow_dim, ZW = 2 * D + Cd;
-  if (V < 1) return set_error(CAREL_ERR_SHAPE, "carel_en_tail_losses: bow_dim must be positive");
-  if ((D & 1) || (Cd & 3)) return set_error(CAREL_ERR_SHAPE, "carel_en_tail_losses: ec_dim must be even and con_dim a multiple of 4");
+  if (V < 1) return set_error(CAREL_ERR_SHAPE, "%s: bow_dim must be positive", who);
+  if ((D & 1) || (Cd & 3)) return set_error(CAREL_ERR_SHAPE, "%s: ec_dim must be even and con_dim a multiple of 4", who);
+  if (bw && !bw->work) return set_error(CAREL_ERR_ARG, "%s: null weight scratch", who);
   if (!a->cdisc_w || !a->cdisc_b || !a->ccls_w || !a->ccls_b || !a->emo_w || !a->emo_b || !a->cau_w || !a->cau_b || !a->pair_w || !a->pair_b ||
       !a->dec_w || !a->dec_b || !a->emo_labels || !a->cau_labels || !a->pair_labels || !a->bow || !a->eps || !a->z || !a->terms || !a->work ||
       !a->d_ccls_w || !a->d_ccls_b || !a->d_emo_w || !a->d_emo_b || !a->d_cau_w || !a->d_cau_b || !a->d_pair_w || !a->d_pair_b || !a->d_dec_w ||
       !a->d_dec_b)
-    return set_error(CAREL_ERR_ARG, "carel_en_tail_losses: null tensor");
-  for (int i = 0; i < 3; ++i) if (!a->g_cdisc_w[i] || !a->g_cdisc_b[i]) return set_error(CAREL_ERR_ARG, "carel_en_tail_losses: null content_disc gradient");
+    return set_error(CAREL_ERR_ARG, "%s: null tensor", who);
+  for (int i = 0; i < 3; ++i) if (!a->g_cdisc_w[i] || !a->g_cdisc_b[i]) return set_error(CAREL_ERR_ARG, "%s: null content_disc gradient", who);
   for (int i = 0; i < 4; ++i)
     if (!a->sdisc_w[i] || !a->sdisc_b[i] || !a->g_sdisc_w[i] || !a->g_sdisc_b[i] || !a->g_sdisc_ent_w[i] || !a->g_sdisc_ent_b[i])
-      return set_error(CAREL_ERR_ARG, "carel_en_tail_losses: null discriminator tensor");
+      return set_error(CAREL_ERR_ARG, "%s: null discriminator tensor", who);
   EnWork w = en_carve((float*)a->work, B, D, Cd, V);
   EnSegs sg;
   for (int s = 0; s < EN_NSEG; ++s) {
@@ -629,20 +706,33 @@ extern "C" int carel_en_tail_losses(const carel_en_tail_args* a, void* stream_) 
   if ((rc = check_launch("en_sample_kernel"))) return rc;
   const float inv_b = 1.0f / (float)B, inv_bv = inv_b / (float)V;
   BowHead h;
+  if (bw) {       // con_w = sigmoid(content_classifier(dropout_120(z_content))), written once; a constant of everything below
+    EnBowWork x = en_bow_carve((float*)bw->work, B, Cd, V);
+    const Dropout d120 = make_dropout(a->drop_seed, 120u, a->drop_p, a->drop_row_offset * (uint32_t)Cd);
+    hipLaunchKernelGGL(en_bow_copy_kernel, dim3((B * Cd + 255) / 256), dim3(256), 0, stream, (const float*)a->z, B, D, Cd, d120, x.xw);
+    if ((rc = check_launch("en_bow_copy_kernel"))) return rc;
+    if ((rc = sgemm(x.xw, Cd, false, (const float*)a->ccls_w, Cd, false, x.conw, V, B, V, Cd, (const float*)a->ccls_b, 0, 1, 0, stream))) return rc;
+    const long n = (long)B * V;
+    const long blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(sigmoid_inplace_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, stream, x.conw, n);
+    if ((rc = check_launch("sigmoid_inplace_kernel"))) return rc;
+    h.wgt = x.conw;
+  }
   // content discriminator on the emotion sample, then on the cause sample (shared weights; the entropy image accumulates)
   for (int i = 0; i < 2; ++i) {
     h.x = w.xd + w.xoff[i]; h.K = D; h.w = (const float*)a->cdisc_w; h.b = (const float*)a->cdisc_b;
     h.s_bce = inv_bv; h.s_ent = inv_b * a->w_con_adv; h.ent = true;
     h.gw = (float*)a->g_cdisc_w[i]; h.gb = (float*)a->g_cdisc_b[i]; h.acc_g = 0;
     h.gew = (float*)a->g_cdisc_w[2]; h.geb = (float*)a->g_cdisc_b[2]; h.acc_ge = i;
-    h.dx = nullptr; h.rowstat = w.rowstat + (size_t)i * B * 2;
+    h.dx = nullptr; h.rowstat = w.rowstat + (size_t)i * B * 2; h.wmode = bw ? BW_ONE_MINUS : BW_NONE;
     if ((rc = bow_head(a, w, h, stream))) return rc;
   }
   // content classifier on the content sample
   h.x = w.xd + w.xoff[2]; h.K = Cd; h.w = (const float*)a->ccls_w; h.b = (const float*)a->ccls_b;
   h.s_bce = inv_bv * a->w_con_mul; h.s_ent = 0.f; h.ent = false; h.gw = (float*)a->d_ccls_w; h.gb = (float*)a->d_ccls_b; h.acc_g = 0;
-  h.gew = nullptr; h.geb = nullptr; h.acc_ge = 0; h.dx = w.dxd_cmul; h.rowstat = w.rowstat + (size_t)2 * B * 2;
+  h.gew = nullptr; h.geb = nullptr; h.acc_ge = 0; h.dx = w.dxd_cmul; h.rowstat = w.rowstat + (size_t)2 * B * 2; h.wmode = bw ? BW_W : BW_NONE;
   if ((rc = bow_head(a, w, h, stream))) return rc;
+  h.wmode = BW_NONE; h.wgt = nullptr;
   // decoder on [emotion, cause, content] (no dropout)
   h.x = (const float*)a->z; h.K = ZW; h.w = (const float*)a->dec_w; h.b = (const float*)a->dec_b;
   h.s_bce = inv_bv; h.gw = (float*)a->d_dec_w; h.gb = (float*)a->d_dec_b; h.dx = w.dz_dec; h.rowstat = w.rowstat + (size_t)3 * B * 2;
@@ -666,13 +756,22 @@ extern "C" int carel_en_tail_losses(const carel_en_tail_args* a, void* stream_) 
   const size_t lds = sizeof(float) * (16 + (size_t)18 * B);
   if (lds > 64 * 1024) {
     hipError_t er = hipFuncSetAttribute((const void*)en_heads_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (er != hipSuccess) return set_error(CAREL_ERR_HIP, "carel_en_tail_losses: hipFuncSetAttribute: %s", hipGetErrorString(er));
+    if (er != hipSuccess) return set_error(CAREL_ERR_HIP, "%s: hipFuncSetAttribute: %s", who, hipGetErrorString(er));
   }
   hipLaunchKernelGGL(en_heads_kernel, dim3(1), dim3(1024), lds, stream, e);
   if ((rc = check_launch("en_heads_kernel"))) return rc;
   hipLaunchKernelGGL(en_dlat_kernel, dim3((B * ZW + 255) / 256), dim3(256), 0, stream, (const float*)w.dz_dec, (const float*)w.dz_heads,
                      (const float*)w.dxd_cmul, sg.d[2], (const float*)a->lat, (const float*)a->eps, B, D, Cd, a->kl_w_ec, a->kl_w_con, w.dlat);
   return check_launch("en_dlat_kernel");
+}
+
+extern "C" int carel_en_tail_losses(const carel_en_tail_args* a, void* stream) {
+  return en_tail_losses(a, nullptr, "carel_en_tail_losses", (hipStream_t)stream);
+}
+
+extern "C" int carel_en_tail_losses_bow(const carel_en_tail_args* a, const carel_en_bow_args* bw, void* stream) {
+  if (!bw) return set_error(CAREL_ERR_ARG, "carel_en_tail_losses_bow: null weight arguments");
+  return en_tail_losses(a, bw, "carel_en_tail_losses_bow", (hipStream_t)stream);
 }
 
 extern "C" int carel_en_tail_backward(const carel_en_tail_args* a, const void* grad_out_dev, void* stream_) {

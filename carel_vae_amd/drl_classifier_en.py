@@ -8,7 +8,12 @@ Same constructor argument, attribute names, state_dict keys, `forward` (returns 
     ... four more discriminator backward calls ...; vae_and_cls_opt.zero_grad(); vae_and_cls_loss.backward()
     six optimiser steps                                                                         (:919-947)
 
-runs unchanged.  All seven losses and every gradient are produced by the forward kernels (the losses are roots of the
+runs unchanged.  The same class covers the reference's other two three-space scripts:
+  opt.language = "zh"   drl_classifier.py: BertModel geometry (hfl/chinese-roberta-wwm-ext), `get_pair_preds` returns the nested list of
+                        rounded 0. / 1. floats (:351), read_ECPE_data also counts the unpredicted emotions, checkpoint best_drl_model_<id>.pt
+  opt.bow_loss = True   drl_classifier_bow_loss.py: the three content losses weighted element by element with
+                        sigmoid(content_classifier(dropout(z_content))) (:245-257) -- carel_en_tail_losses_bow; no extra parameter
+All seven losses and every gradient are produced by the forward kernels (the losses are roots of the
 graph); a discriminator's backward call only adds its share into `.grad`, the last one runs the encoder backward.
 No CPU fallback: CPU tensors raise.
 """
@@ -54,9 +59,45 @@ def make_opt(**kw):
     return SimpleNamespace(**d)
 
 
-def read_ECPE_data(file_path, test=False, rng=random):
+def make_zh_opt(**kw):
+    """The argparse namespace of drl_classifier.py (:29-61): the defaults above except the corpus file and the language switch."""
+    d = dict(DEFAULT_OPT, language="zh", bow_file="data/all_data_pair.txt", self_iteration=30, model_id="carel-zh3")
+    d.update(kw)
+    return SimpleNamespace(**d)
+
+
+def make_bow_loss_opt(**kw):
+    """The argparse namespace of drl_classifier_bow_loss.py (:29-61): the zh defaults with 50 self-training iterations (:55), plus the
+    switch that selects that script's weighted content losses here."""
+    d = dict(DEFAULT_OPT, language="zh", bow_file="data/all_data_pair.txt", self_iteration=50, model_id="carel-zh3-bow", bow_loss=True)
+    d.update(kw)
+    return SimpleNamespace(**d)
+
+
+_BOW_LOSS_VALUES = {False: False, "false": False, True: True, "true": True}
+
+
+def bow_loss_config(opt):
+    """opt.bow_loss -> bool; anything but False / True / "false" / "true" is refused by name."""
+    v = getattr(opt, "bow_loss", False)
+    if not isinstance(v, (bool, str)) or v not in _BOW_LOSS_VALUES:
+        raise L.CarelError("opt.bow_loss must be False, True, \"false\" or \"true\" (got %r)" % (v,))
+    return _BOW_LOSS_VALUES[v]
+
+
+def checkpoint_name(opt):
+    """File name of the best-model checkpoint: best_drl_en_model_<id>.pt (drl_classifier_en.py:651), best_drl_model_<id>.pt for the two
+    zh scripts (drl_classifier.py:647)."""
+    return ("best_drl_model_" if getattr(opt, "language", "en") == "zh" else "best_drl_en_model_") + str(opt.model_id) + ".pt"
+
+
+def read_ECPE_data(file_path, test=False, rng=random, language="en"):
     """drl_classifier_en.py:748-813: (df[pair, label], docs_pair_size).  Same row order and the same use of random.sample for
-    the training negatives, so `random.seed(42)` (:26) reproduces the reference's rows; test=True keeps every negative."""
+    the training negatives, so `random.seed(42)` (:26) reproduces the reference's rows; test=True keeps every negative.
+    language="zh": the reader of drl_classifier.py (:652-742), which also counts the emotions the test split leaves unpredicted --
+    (df, docs_pair_size, num_unpred_emotions), carel_vae_amd.data.read_ECPE_data."""
+    if language == "zh":
+        return _data.read_ECPE_data(file_path, test=test, language="zh", rng=rng)
     rows, docs_pair_size = [], []
     with open(file_path, encoding="utf8") as f:
         while True:
@@ -124,11 +165,17 @@ class DrlClassifier(_Base):
     TERM_NAMES = TERM_NAMES
 
     def __init__(self, opt, encoder_cfg=None, seed=None):
-        if encoder_cfg is None:
-            encoder_cfg = encoder_config("en")
+        language = getattr(opt, "language", "en")
+        if language not in ("en", "zh"):
+            raise L.CarelError("opt.language must be \"en\" or \"zh\" (got %r)" % (language,))
+        bow_loss = bow_loss_config(opt)
         if getattr(opt, "adapter", "false") not in ("false", False, None):
-            raise L.CarelError("drl_classifier_en.py has no sentence adapters (opt.adapter belongs to the EMNLP scripts' model)")
+            raise L.CarelError("drl_classifier_en.py has no sentence adapters (opt.adapter belongs to the EMNLP scripts' model)"
+                               + (": opt.bow_loss cannot be combined with opt.adapter" if bow_loss else ""))
+        if encoder_cfg is None:
+            encoder_cfg = encoder_config(language)
         super().__init__(opt, encoder_cfg=encoder_cfg, seed=seed)
+        self.language, self.bow_loss = language, bow_loss
         self._has_pair_skip = False          # this script has no "pair loss replaced by 0" branch (:587-603)
 
     def _build_heads(self, opt):
@@ -245,6 +292,8 @@ class DrlClassifier(_Base):
                 z=torch.empty(B, 2 * o.ec_dim + o.con_dim, device=dev), terms=torch.zeros(32, device=dev),
                 work=torch.empty(lib.carel_en_tail_workspace_floats(B, o.ec_dim, o.con_dim, o.pair_bow_dim), device=dev),
                 dx_last=torch.empty(Bp * S, H, device=dev))
+            if self.bow_loss:       # the site-120 copy of the content sample and the weight matrix [B, V]
+                buf.bow_work = ops.en_bow_workspace(B, o.con_dim, o.pair_bow_dim, dev)
             self._ws[key] = buf
         c.buf = buf
         return c
@@ -317,7 +366,10 @@ class DrlClassifier(_Base):
             cls_rows, n_rows = (None, c.Bp * c.S) if c.pack is None else (c.pack.cu, c.pack.n_tokens)
         ta = self._en_tail_args(c, x_last_ptr, cls_rows, n_rows, train_drop)
         L.check(lib.carel_en_tail_latents(C.byref(ta), st), "carel_en_tail_latents")
-        L.check(lib.carel_en_tail_losses(C.byref(ta), st), "carel_en_tail_losses")
+        if self.bow_loss:
+            ops.en_tail_losses_bow(ta, ops.en_bow_args(c.buf.bow_work))
+        else:
+            L.check(lib.carel_en_tail_losses(C.byref(ta), st), "carel_en_tail_losses")
         c.ea, c.ta, c.ws = ea, ta, ws
         c.keep = (cls_rows,)
 
@@ -458,9 +510,17 @@ class DrlClassifier(_Base):
     def pair_probabilities(self, input_ids, att_masks, token_type_ids, chunk=1024):
         return torch.sigmoid(self.pair_logits(input_ids, att_masks, token_type_ids, chunk))
 
-    def get_pair_preds(self, input_ids, att_masks, token_type_ids):
-        """Reference `get_pair_preds` (:336-353): the raw logits, a [N, 1] tensor."""
-        return self.pair_logits(input_ids, att_masks, token_type_ids).reshape(-1, 1)
+    def get_pair_preds(self, input_ids, att_masks, token_type_ids, round=True):
+        """Reference `get_pair_preds` (:336-353): the raw logits, a [N, 1] tensor.  opt.language "zh": the nested python list
+        [[0.|1.], ...] of drl_classifier.py:351 (round=False: the probabilities, same nesting)."""
+        logits = self.pair_logits(input_ids, att_masks, token_type_ids).reshape(-1, 1)
+        if self.language != "zh":
+            return logits
+        prob = torch.sigmoid(logits).cpu().detach().numpy()
+        return (prob.round() if round else prob).tolist()
+
+    def checkpoint_name(self):
+        return checkpoint_name(self.opt)
 
     def get_annealed_weight(self, iteration, lambda_weight):
         return (math.tanh((iteration - self.opt.kl_ann_iterations * 1.5) / (self.opt.kl_ann_iterations / 3)) + 1) * lambda_weight

@@ -304,6 +304,27 @@ def adapter_backward_weights(a, g):
     L.check(L.load().carel_adapter_backward_weights(C.byref(a), C.byref(g), L.current_stream()), "carel_adapter_backward_weights")
 
 
+def en_bow_workspace(batch, con_dim, bow_dim, device):
+    """Scratch of carel_en_tail_losses_bow: the site-120 copy of the content sample [B, con_dim], then the weight matrix [B, V]."""
+    return torch.empty(L.load().carel_en_tail_bow_workspace_floats(batch, con_dim, bow_dim), device=device, dtype=torch.float32)
+
+
+def en_bow_args(work):
+    """carel_en_bow_args around a scratch tensor from en_bow_workspace (kept alive by the returned struct)."""
+    _chk_cuda(work)
+    if work.dtype != torch.float32 or not work.is_contiguous():
+        raise L.CarelError("the weight scratch must be a contiguous f32 tensor")
+    b = L.EnBowArgs()
+    b.work = work.data_ptr()
+    b._keep = work
+    return b
+
+
+def en_tail_losses_bow(a, b):
+    """carel_en_tail_losses with the element-weighted content losses of drl_classifier_bow_loss.py; a: EnTailArgs, b: en_bow_args(...)."""
+    L.check(L.load().carel_en_tail_losses_bow(C.byref(a), C.byref(b), L.current_stream()), "carel_en_tail_losses_bow")
+
+
 def _vi_args(z, net):
     _chk_cuda(z, *net)
     if z.dtype != torch.float32 or not z.is_contiguous() or z.dim() != 2 or z.shape[1] % 2:

@@ -850,6 +850,26 @@ int64_t carel_en_tail_workspace_floats(int32_t batch, int32_t ec_dim, int32_t co
 int carel_en_tail_latents(const carel_en_tail_args* args, void* stream);     /* pooled, lat (also the front of get_pair_preds, :336-349) */
 int carel_en_tail_losses(const carel_en_tail_args* args, void* stream);      /* z, terms and every gradient listed above */
 int carel_en_tail_backward(const carel_en_tail_args* args, const void* grad_out_dev_f32, void* stream);
+/* The same tail with the ELEMENT-WEIGHTED content losses of drl_classifier_bow_loss.py (:245-257, :438-448, :537-550):
+ *   con_w = sigmoid(content_classifier(dropout(z_content)))        [B, V]; its own dropout draw, DETACHED
+ *   content_disc_loss_{emo,cau} = BCELoss(weight = 1 - con_w)(softmax(content_disc(dropout(z_{e,c}))), smoothed_bow)
+ *   content_mul_loss            = BCELoss(weight = con_w)    (softmax(content_classifier(dropout(z_content))), smoothed_bow)
+ * With p the softmax row, t the smoothed target and omega the weight, the row statistic is sum_j omega_j * bce_j (both logs
+ * clamped at -100 before the multiply, as nn.BCELoss does), reduced by the plain mean over B * V (not by sum omega), and
+ *   d loss / d logit_j = p_j * (omega_j * g_j - sum_k p_k * omega_k * g_k) / (B * V),   g = (p - t) / (p * (1 - p)).
+ * The weight is a constant: nothing flows into content_classifier or z_content through it.  Entropies, decoder, one-logit
+ * heads, KL terms and the weighted sum are those of carel_en_tail_losses, bit for bit; terms[], every gradient image and
+ * `work` have the same meaning, so carel_en_tail_backward follows unchanged.
+ * The weight input is an eleventh dropped-out copy of the content sample at dropout SITE 120 (sites 110..119 keep their
+ * meaning; drop_row_offset applies to it like to the others).  One fp32 GEMM [B, con_dim] x [con_dim, V] and one
+ * element-wise pass write con_w ONCE into the scratch below; the row passes of the three heads read it.
+ * Errors before any launch: NULL `bow` / `bow->work` -> CAREL_ERR_ARG; a shape outside carel_en_tail_losses' range
+ * (batch 1..1024, ...) -> CAREL_ERR_SHAPE. */
+typedef struct carel_en_bow_args {
+  void* work;                        /* f32 [carel_en_tail_bow_workspace_floats(...)]: site-120 copy [B, con_dim], then con_w [B, V] */
+} carel_en_bow_args;
+int64_t carel_en_tail_bow_workspace_floats(int32_t batch, int32_t con_dim, int32_t bow_dim);
+int carel_en_tail_losses_bow(const carel_en_tail_args* args, const carel_en_bow_args* bow, void* stream);
 /* get_pair_preds (:336-353): raw pair logits from lat with fresh emotion / cause noise (f32 [ec_dim] each) */
 int carel_en_pair_logits(const void* lat, int32_t lat_stride, int32_t emo_off, int32_t cau_off, const void* eps_e, const void* eps_c,
                          const void* pair_w, const void* pair_b, int32_t batch, int32_t ec_dim, void* logits, void* stream);
