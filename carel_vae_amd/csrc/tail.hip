@@ -10,39 +10,10 @@
 #include "mmd_device.h"
 #include "hsic_device.h"
 #include "rowvec_device.h"
+#include "tail_device.h"
 
 namespace carel {
 
-// ------------------------------------------------------------------------------------------
-// Tail core: one workgroup.  lat = [mu_e | lv_e | mu_c | lv_c] (B x 4D).
-// ------------------------------------------------------------------------------------------
-struct TailCore {
-  int B, D, EC;                 // batch, ec_dim (<= 32), emotion classes (<= 8)
-  const float* lat;             // [B, 4D]
-  const float* eps_e; const float* eps_c;
-  const float* emo_w; const float* emo_b;      // [EC, D], [EC]
-  const float* cau_w; const float* cau_b;      // [1, D], [1]
-  const float* pair_w; const float* pair_b;    // [1, 2D], [1]
-  const long* emo_labels; const float* cau_labels; const float* pair_labels;
-  float w_mmd, w_emo, w_cau, w_pair, kl_w, ls;
-  int dis_mode;                 // 0: -w_mmd * RBF-MMD (ref :231-233); 1: +w_mmd * HSIC (drl_classifier_ec_hsic.py:214); 2: none
-  int emo_bce;                  // 1: one-logit sigmoid + BCE emotion head (ec_hsic/ec_vi scripts) instead of the softmax CE
-  Dropout d_emo, d_cau, d_pair;                // element index b*D + k (pair: b*2D + k)
-  float alpha, mmd_eps;
-  const float* label_sum_override; float n_override;   // global-batch pos_weight (DP); null/0 = local
-  int label_sum_ranks;          // > 1: the global label sum is the sum of this many floats, rank_stride apart
-  const float* z_global; int n_global, row_offset; float mmd_grad_scale;  // global-batch MMD (DP)
-  int rank_stride;              // floats between consecutive ranks' blocks of B rows in z_global (B*2D when dense)
-  const float* mmd_part; int mmd_nblk; const float* dz_mmd;   // global-batch MMD computed by mmd_global_kernel (else null)
-  // outputs
-  float* z;                     // [B, 2D]; null = do not write it (the caller's own sample_z_kernel did: overlapped tail)
-  float* terms;                 // [16]: 0 partial loss (everything but rec), 1 mmd, 2 emo, 3 cau, 4 pair, 5 kl_e, 6 kl_c
-  float* dz;                    // [B, 2D]  d(loss)/dz (without reconstruction)
-  float* dlat_direct;           // [B, 4D]  KL part of d(loss)/d lat
-  float* d_emo_w; float* d_emo_b; float* d_cau_w; float* d_cau_b; float* d_pair_w; float* d_pair_b;
-  float* pair_dead;             // [1]: 1.0 if the pair loss was replaced by 0 (ref :510-511)
-  long long* prof;              // diagnostics (carel_tail_profile): phase time stamps, or null
-};
 #define TAIL_STAMP(i) do { if (a.prof && threadIdx.x == 0) a.prof[i] = (long long)wall_clock64(); } while (0)
 
 // ------------------------------------------------------------------------------------------
@@ -165,10 +136,9 @@ __global__ __launch_bounds__(1024) void tail_core_kernel(TailCore a) {
   float* mlt = gx + B * 2;                       // [B][4D] dropout multipliers: emotion [D] | cause [D] | pair [2D]
   float* lg = mlt + B * D4;                      // [B][16] head logits: emotion classes, then cause, then pair
   float* hw = lg + B * 16;                       // head weights: emo_w [EC*D], emo_b [EC], cau_w [D], cau_b, pair_w [2D], pair_b
-  const int n_emo = a.EC * D;
-  const int o_eb = n_emo, o_cw = o_eb + a.EC, o_cb = o_cw + D, o_pw = o_cb + 1, o_pb = o_pw + D2, n_hw = o_pb + 1;
+  const HeadLayout L(a.EC, D);
   const int nm = a.z_global ? a.n_global : B;    // samples per side in the MMD
-  float* nrm = hw + ((n_hw + 3) & ~3);           // [2 nm]
+  float* nrm = hw + ((L.n + 3) & ~3);            // [2 nm]
   float* Z = nrm + ((2 * nm + 3) & ~3);          // MMD samples [2 nm][D|1]
   const int zs = D | 1;
   const int t = threadIdx.x;
@@ -176,18 +146,12 @@ __global__ __launch_bounds__(1024) void tail_core_kernel(TailCore a) {
 
   for (int e = t; e < B * D2; e += blockDim.x) {
     const int b = e / D2, k = e - b * D2;
-    const float* row = a.lat + (long)b * 4 * D;
-    const float z = (k < D) ? row[k] + a.eps_e[k] * expf(row[D + k]) : row[2 * D + (k - D)] + a.eps_c[k - D] * expf(row[3 * D + (k - D)]);
+    const float z = sample_z(a.lat + (long)b * 4 * D, a.eps_e, a.eps_c, D, k);
     zl[e] = z; dzl[e] = 0.f;
     if (a.z) a.z[e] = z;
   }
-  for (int e = t; e < B * D4; e += blockDim.x) {
-    const int b = e / D4, k = e - b * D4;
-    mlt[e] = k < D ? dropout_mult(a.d_emo, b * D + k) : (k < D2 ? dropout_mult(a.d_cau, b * D + (k - D)) : dropout_mult(a.d_pair, b * D2 + (k - D2)));
-  }
-  for (int e = t; e < n_hw; e += blockDim.x)
-    hw[e] = e < o_eb ? a.emo_w[e] : e < o_cw ? a.emo_b[e - o_eb] : e < o_cb ? a.cau_w[e - o_cw] : e < o_pw ? a.cau_b[0]
-          : e < o_pb ? a.pair_w[e - o_pw] : a.pair_b[0];
+  fill_dropout_mults(a, mlt, 0, B, t, blockDim.x);
+  load_head_weights(a, L, hw, t, blockDim.x);
   __syncthreads();
   // ---- MMD samples: rows [0,nm) emotion, [nm,2nm) cause   (not needed when mmd_global_kernel did the statistic)
   for (int e = t; e < (a.mmd_part ? 0 : 2 * nm * D); e += blockDim.x) {
@@ -200,13 +164,8 @@ __global__ __launch_bounds__(1024) void tail_core_kernel(TailCore a) {
   float mmd = 0.f;                     // value of the disentanglement statistic (terms[1])
   float dis_term = 0.f;                // its contribution to the loss
   if (a.dis_mode == 0 && a.mmd_part) {
-    // partial block sums in fixed order (double accumulation as in mmd_forward_block), gradient rows already computed
-    if (t == 0) {
-      double s11 = 0.0, s22 = 0.0, s12 = 0.0;
-      for (int q = 0; q < a.mmd_nblk; ++q) { s11 += a.mmd_part[q * 4]; s22 += a.mmd_part[q * 4 + 1]; s12 += a.mmd_part[q * 4 + 2]; }
-      const double b00 = 1.0 / ((double)nm * (nm - 1)), b01 = -1.0 / ((double)nm * nm);
-      sc[0] = (float)(2.0 * b01 * s12 + b00 * s11 + b00 * s22);
-    }
+    // mmd_global_kernel's partials; the gradient rows are already computed
+    if (t == 0) sc[0] = mmd_from_partials(a, nm);
     __syncthreads();
     mmd = sc[0];
     dis_term = -a.w_mmd * mmd;
@@ -261,86 +220,32 @@ __global__ __launch_bounds__(1024) void tail_core_kernel(TailCore a) {
   // ---- classifier heads: 16 threads per sample, one per logit (emotion classes, cause, pair)
   for (int e = t; e < B * 16; e += blockDim.x) {
     const int b = e >> 4, h = e & 15;
-    if (h < a.EC) {
-      float s = hw[o_eb + h];
-      for (int k = 0; k < D; ++k) s = fmaf(hw[h * D + k], zl[b * D2 + k] * mlt[b * D4 + k], s);
-      lg[e] = s;
-    } else if (h == a.EC) {
-      float s = hw[o_cb];
-      for (int k = 0; k < D; ++k) s = fmaf(hw[o_cw + k], zl[b * D2 + D + k] * mlt[b * D4 + D + k], s);
-      lg[e] = s;
-    } else if (h == a.EC + 1) {
-      float s = hw[o_pb];
-      for (int k = 0; k < D2; ++k) s = fmaf(hw[o_pw + k], zl[b * D2 + k] * mlt[b * D4 + D2 + k], s);
-      lg[e] = s;
-    }
+    if (h < a.EC + 2) lg[e] = head_logit(a, L, hw, zl, mlt, b, h);
   }
   float l_emo = 0.f, l_cau = 0.f, l_pair = 0.f, ysum = 0.f;
   if (t < B) ysum = a.pair_labels[t];
   ysum = block_sum(t < B ? ysum : 0.f, red);        // (its barriers also publish lg)
-  const float ntot = a.label_sum_override ? a.n_override : (float)B;
-  float ytot = ysum;
-  if (a.label_sum_override) {
-    ytot = a.label_sum_override[0];
-    for (int r = 1; r < a.label_sum_ranks; ++r) ytot += a.label_sum_override[(long)r * a.rank_stride];
-  }
-  const float pw = (ntot - ytot) / ytot;        // inf when there is no positive in the batch
-  float xp = 0.f, tp = 0.f;
-  for (int b = t; b < B; b += blockDim.x) {
-    if (!a.emo_bce) {
-      // emotion: CE(W (z_e * m) + b, label)
-      float mx = -INFINITY;
-      for (int c = 0; c < a.EC; ++c) mx = fmaxf(mx, lg[b * 16 + c]);
-      float se = 0.f;
-      for (int c = 0; c < a.EC; ++c) se += expf(lg[b * 16 + c] - mx);
-      const float lse = mx + logf(se);
-      long lab = a.emo_labels[b]; lab = lab < 0 ? 0 : (lab >= a.EC ? a.EC - 1 : lab);
-      l_emo += lse - lg[b * 16 + lab];
-      for (int c = 0; c < a.EC; ++c) elog[b * 8 + c] = (expf(lg[b * 16 + c] - lse) - (c == lab ? 1.f : 0.f)) * (a.w_emo / B);
-    } else {
-      // emotion, 1-logit variant: BCE(sigmoid(w (z_e * m) + b), smoothed label)   (drl_classifier_ec_hsic.py:455-470)
-      const float pe = 1.0f / (1.0f + expf(-lg[b * 16]));
-      const float te = (float)a.emo_labels[b] * (1.f - a.ls) + a.ls;
-      l_emo += -(te * fmaxf(logf(pe), -100.f) + (1.f - te) * fmaxf(logf(1.f - pe), -100.f));
-      const float gpe = (pe - te) / fmaxf((1.f - pe) * pe, 1e-12f);
-      elog[b * 8] = gpe * pe * (1.f - pe) * (a.w_emo / B);
-    }
-    // cause: BCE(sigmoid(w (z_c * m) + b), smoothed)
-    const float pc = 1.0f / (1.0f + expf(-lg[b * 16 + a.EC]));
-    const float tc = a.cau_labels[b] * (1.f - a.ls) + a.ls;
-    l_cau += -(tc * fmaxf(logf(pc), -100.f) + (1.f - tc) * fmaxf(logf(1.f - pc), -100.f));
-    const float gp = (pc - tc) / fmaxf((1.f - pc) * pc, 1e-12f);
-    gx[b * 2] = gp * pc * (1.f - pc) * (a.w_cau / B);
-    // pair: BCEWithLogits(w (z * m) + b, smoothed, pos_weight)
-    xp = lg[b * 16 + a.EC + 1];
-    tp = a.pair_labels[b] * (1.f - a.ls) + a.ls;
-    const float lw = (pw - 1.f) * tp + 1.f;
-    l_pair += (1.f - tp) * xp + lw * (log1pf(expf(-fabsf(xp))) + fmaxf(-xp, 0.f));
+  const float pw = pair_pos_weight(a, ysum);
+  for (int b = t; b < B; b += blockDim.x) {          // losses and dlogits of a row in one trip (the pair dlogit waits for `dead`)
+    const float* lr = lg + b * 16;
+    emo_row<true, true>(a, lr, b, l_emo, elog + b * 8);
+    l_cau += cau_row_loss(a, lr, b);
+    gx[b * 2] = cau_row_dlogit(a, lr, b);
+    l_pair += pair_row_loss(a, lr, b, pw);
   }
   l_emo = block_sum(l_emo, red) / B;
   l_cau = block_sum(l_cau, red) / B;
   l_pair = block_sum(l_pair, red) / B;
   const bool dead = isinf(l_pair);
   if (dead) l_pair = 0.f;
-  for (int b = t; b < B; b += blockDim.x) {
-    const float xb = lg[b * 16 + a.EC + 1], tb = a.pair_labels[b] * (1.f - a.ls) + a.ls;
-    const float lw = (pw - 1.f) * tb + 1.f;
-    const float sg = 1.0f / (1.0f + expf(-xb));
-    gx[b * 2 + 1] = dead ? 0.f : ((1.f - tb) - lw * (1.f - sg)) * (a.w_pair / B);
-  }
+  for (int b = t; b < B; b += blockDim.x) gx[b * 2 + 1] = pair_row_dlogit(a, lg + b * 16, b, pw, dead);
   __syncthreads();
   TAIL_STAMP(4);
   // ---- KL (:525-534) and its direct gradient on lat
   float kle = 0.f, klc = 0.f;
   for (int e = t; e < B * D; e += blockDim.x) {
     const int b = e / D, k = e - b * D;
-    const float* row = a.lat + (long)b * 4 * D;
-    const float mue = row[k], lve = row[D + k], muc = row[2 * D + k], lvc = row[3 * D + k];
-    kle += -0.5f * (1.f + lve - expf(lve) - mue * mue);
-    klc += -0.5f * (1.f + lvc - expf(lvc) - muc * muc);
-    float* dl = a.dlat_direct + (long)b * 4 * D;
-    dl[k] = a.kl_w * mue / B; dl[D + k] = a.kl_w * (-0.5f) * (1.f - expf(lve)) / B;
-    dl[2 * D + k] = a.kl_w * muc / B; dl[3 * D + k] = a.kl_w * (-0.5f) * (1.f - expf(lvc)) / B;
+    kl_row(a, b, k, kle, klc);
   }
   kle = block_sum(kle, red) / B * a.kl_w;
   klc = block_sum(klc, red) / B * a.kl_w;
@@ -348,92 +253,15 @@ __global__ __launch_bounds__(1024) void tail_core_kernel(TailCore a) {
   // ---- dz from the three heads, and the head parameter gradients
   for (int e = t; e < B * D2; e += blockDim.x) {
     const int b = e / D2, k = e - b * D2;
-    float g = hw[o_pw + k] * gx[b * 2 + 1] * mlt[b * D4 + D2 + k];
-    if (k < D) {
-      float s = 0.f;
-      for (int c = 0; c < a.EC; ++c) s = fmaf(hw[c * D + k], elog[b * 8 + c], s);
-      g += s * mlt[b * D4 + k];
-    } else {
-      g += hw[o_cw + (k - D)] * gx[b * 2] * mlt[b * D4 + k];
-    }
-    dzl[e] += g;
+    dzl[e] += heads_dz(a, L, hw, mlt, elog, gx, b, k);
   }
   TAIL_STAMP(6);
   // parameter gradients: thread per parameter element, loop over the batch (fixed order)
-  for (int e = t; e < n_hw; e += blockDim.x) {
-    float s = 0.f;
-    if (e < o_eb) {
-      const int c = e / D, k = e - c * D;
-      for (int b = 0; b < B; ++b) s = fmaf(elog[b * 8 + c], zl[b * D2 + k] * mlt[b * D4 + k], s);
-      a.d_emo_w[e] = s;
-    } else if (e < o_cw) {
-      const int c = e - o_eb;
-      for (int b = 0; b < B; ++b) s += elog[b * 8 + c];
-      a.d_emo_b[c] = s;
-    } else if (e < o_cb) {
-      const int k = e - o_cw;
-      for (int b = 0; b < B; ++b) s = fmaf(gx[b * 2], zl[b * D2 + D + k] * mlt[b * D4 + D + k], s);
-      a.d_cau_w[k] = s;
-    } else if (e == o_cb) {
-      for (int b = 0; b < B; ++b) s += gx[b * 2];
-      a.d_cau_b[0] = s;
-    } else if (e < o_pb) {
-      const int k = e - o_pw;
-      for (int b = 0; b < B; ++b) s = fmaf(gx[b * 2 + 1], zl[b * D2 + k] * mlt[b * D4 + D2 + k], s);
-      a.d_pair_w[k] = s;
-    } else {
-      for (int b = 0; b < B; ++b) s += gx[b * 2 + 1];
-      a.d_pair_b[0] = s;
-    }
-  }
+  for (int e = t; e < L.n; e += blockDim.x) *head_grad_dst(a, L, e) = head_param_grad(a, L, zl, mlt, elog, gx, e, B);
   __syncthreads();
   TAIL_STAMP(7);
   for (int e = t; e < B * D2; e += blockDim.x) a.dz[e] = dzl[e];
-  if (t == 0) {
-    a.terms[1] = mmd; a.terms[2] = l_emo; a.terms[3] = l_cau; a.terms[4] = l_pair; a.terms[5] = kle; a.terms[6] = klc;
-    a.terms[0] = dis_term + a.w_emo * l_emo + a.w_cau * l_cau + a.w_pair * l_pair + kle + klc;
-    a.pair_dead[0] = dead ? 1.f : 0.f;
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// Decoder: logits[b][j] = z[b] . Wd[j] + bd[j] ; p = softmax_j ; rec = mean_{b,j} BCE(p, 0.9 bow + 0.1/V)
-// Work is split over chunks of DEC_J vocabulary entries (one thread per entry holding its 2D weights in
-// registers, the batch's latents in LDS).  Three passes (row max/sum, loss + softmax-backward dot,
-// gradients); partial results are combined in fixed order so the result is run-to-run reproducible.
-// ------------------------------------------------------------------------------------------
-constexpr int DEC_J = 128;          // vocabulary entries per workgroup
-constexpr int DEC_MAXD2 = 64;
-constexpr int DEC_MAXG = 4;         // sample groups per workgroup (threads = DEC_J * groups)
-
-struct DecArgs {
-  int B, D2, V;
-  const float* z;          // [B, D2]
-  const float* w; const float* b;          // [V, D2], [V]
-  const float* bow;        // [B, V]
-  float ls;
-  float* part;             // pass1: [chunks][B][2] (max, sumexp) ; pass2: [chunks][B][2] (loss, dot)
-  float* rowstat;          // [B][4]: M, log L, dot, loss-sum
-  float* dz_part;          // [chunks][B][D2]
-  float* dw; float* db;    // [V, D2], [V]
-  float gscale;            // 1/(B V)
-};
-
-template <int CD2>
-__device__ __forceinline__ float dec_logit(const float* wr, const float* zrow, int D2rt, float bias) {
-  const int D2 = CD2 ? CD2 : D2rt;
-  float s = bias;
-  if (CD2 && (CD2 & 3) == 0) {
-#pragma unroll
-    for (int k = 0; k < D2; k += 4) {
-      const float4 zv = *(const float4*)(zrow + k);          // LDS broadcast read, 16 B
-      s = fmaf(wr[k], zv.x, s); s = fmaf(wr[k + 1], zv.y, s); s = fmaf(wr[k + 2], zv.z, s); s = fmaf(wr[k + 3], zv.w, s);
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < D2; ++k) s = fmaf(wr[k], zrow[k], s);
-  }
-  return s;
+  if (t == 0) write_terms(a, mmd, dis_term, l_emo, l_cau, l_pair, kle, klc, dead);
 }
 
 // CD2 > 0: 2*ec_dim known at compile time (weights stay in registers); CD2 == 0: generic run-time width.
@@ -484,10 +312,7 @@ __global__ __launch_bounds__(DEC_J * DEC_MAXG) void decoder_kernel(DecArgs a) {
           float le = 0.f, dt = 0.f;
           if (live) {
             const float lp = dec_logit<CD2>(wr, zl + b * D2, D2, bias) - a.rowstat[b * 4] - a.rowstat[b * 4 + 1];
-            const float p = expf(lp);
-            const float tg = bw[u] * (1.f - a.ls) + a.ls / a.V;
-            le = -(tg * fmaxf(lp, -100.f) + (1.f - tg) * fmaxf(log1pf(-p), -100.f));
-            dt = p * ((p - tg) / fmaxf((1.f - p) * p, 1e-12f));
+            dec_loss_dot(lp, dec_target(a, bw[u]), le, dt);
           }
           tile[b * DEC_J + tj] = le; tile2[b * DEC_J + tj] = dt;
         }
@@ -513,8 +338,7 @@ __global__ __launch_bounds__(DEC_J * DEC_MAXG) void decoder_kernel(DecArgs a) {
           if (live) {
             const float lp = dec_logit<CD2>(wr, zl + b * D2, D2, bias) - a.rowstat[b * 4] - a.rowstat[b * 4 + 1];
             const float p = expf(lp);
-            const float tg = bw[u] * (1.f - a.ls) + a.ls / a.V;
-            const float gp = (p - tg) / fmaxf((1.f - p) * p, 1e-12f);
+            const float gp = bce_dprob(p, dec_target(a, bw[u]));
             gg = p * (gp - a.rowstat[b * 4 + 2]) * a.gscale;
             _Pragma("unroll") for (int k = 0; k < D2; ++k) dwr[k] = fmaf(gg, zl[b * D2 + k], dwr[k]);
             dbj += gg;
@@ -615,14 +439,13 @@ __global__ __launch_bounds__(256) void tail_dlat_kernel(const float* __restrict_
   dlat[(long)b * 4 * D + (2 * side + 1) * D + kk] = (dlat_direct[(long)b * 4 * D + (2 * side + 1) * D + kk] + g * ep * expf(lv)) * gout;
 }
 
-// z = [mu_e + eps_e * exp(lv_e) | mu_c + eps_c * exp(lv_c)]   (sample_prior :345-351; same expression as in tail_core_kernel)
+// z = [mu_e + eps_e * exp(lv_e) | mu_c + eps_c * exp(lv_c)]   (sample_prior :345-351)
 __global__ __launch_bounds__(256) void sample_z_kernel(const float* __restrict__ lat, const float* __restrict__ eps_e,
                                                        const float* __restrict__ eps_c, int B, int D, float* __restrict__ z) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= B * 2 * D) return;
   const int b = e / (2 * D), k = e - b * 2 * D;
-  const float* row = lat + (long)b * 4 * D;
-  z[e] = (k < D) ? row[k] + eps_e[k] * expf(row[D + k]) : row[2 * D + (k - D)] + eps_c[k - D] * expf(row[3 * D + (k - D)]);
+  z[e] = sample_z(lat + (long)b * 4 * D, eps_e, eps_c, D, k);
 }
 
 // eval-mode pair probabilities (get_pair_preds :265-282): sigmoid(w . [mu_e + eps_e e^lv_e, mu_c + eps_c e^lv_c] + b)
@@ -634,8 +457,8 @@ __global__ __launch_bounds__(256) void pair_prob_kernel(const float* __restrict_
   const float* row = lat + (long)b * 4 * D;
   float s = bias[0];
   for (int k = 0; k < D; ++k) {
-    s = fmaf(w[k], row[k] + eps_e[k] * expf(row[D + k]), s);
-    s = fmaf(w[D + k], row[2 * D + k] + eps_c[k] * expf(row[3 * D + k]), s);
+    s = fmaf(w[k], reparam(row[k], eps_e[k], row[D + k]), s);
+    s = fmaf(w[D + k], reparam(row[2 * D + k], eps_c[k], row[3 * D + k]), s);
   }
   prob[b] = 1.0f / (1.0f + expf(-s));
 }
@@ -656,7 +479,7 @@ constexpr int TT_R = 64;            // rows per slab
 constexpr int TT_THREADS = 256;
 constexpr int TT_MAX_B = 1024;
 constexpr int TT_MAX_SLABS = TT_MAX_B / TT_R;
-constexpr int TT_MAX_NHW = 8 * 32 + 8 + 32 + 1 + 64 + 1;     // head parameters at ec_dim 32, 8 classes
+constexpr int TT_MAX_NHW = HeadLayout(8, 32).n;                // head parameters at ec_dim 32, 8 classes
 
 struct TailTiled {
   TailCore c;              // c.z: the batch's sampled latents, already written by sample_z_kernel
@@ -677,37 +500,20 @@ __global__ __launch_bounds__(TT_THREADS) void tail_heads_kernel(TailTiled q) {
   float* elog = lg + TT_R * 16;                  // [R][8] emotion dlogits
   float* gx = elog + TT_R * 8;                   // [R][2] cause / pair dlogit
   float* hw = gx + TT_R * 2;                     // head weights, as in tail_core_kernel
-  const int n_emo = a.EC * D;
-  const int o_eb = n_emo, o_cw = o_eb + a.EC, o_cb = o_cw + D, o_pw = o_cb + 1, o_pb = o_pw + D2, n_hw = o_pb + 1;
+  const HeadLayout L(a.EC, D);
   const int t = threadIdx.x;
   const int r0 = blockIdx.x * TT_R, nr = min(TT_R, B - r0);       // this slab: rows r0 .. r0 + nr - 1
   const int nslab = gridDim.x;
 
   for (int e = t; e < nr * D2; e += TT_THREADS) zl[e] = a.z[(long)r0 * D2 + e];
-  for (int e = t; e < nr * D4; e += TT_THREADS) {
-    const int b = r0 + e / D4, k = e % D4;                        // dropout streams by the element index of the whole batch
-    mlt[e] = k < D ? dropout_mult(a.d_emo, b * D + k) : (k < D2 ? dropout_mult(a.d_cau, b * D + (k - D)) : dropout_mult(a.d_pair, b * D2 + (k - D2)));
-  }
-  for (int e = t; e < n_hw; e += TT_THREADS)
-    hw[e] = e < o_eb ? a.emo_w[e] : e < o_cw ? a.emo_b[e - o_eb] : e < o_cb ? a.cau_w[e - o_cw] : e < o_pw ? a.cau_b[0]
-          : e < o_pb ? a.pair_w[e - o_pw] : a.pair_b[0];
+  fill_dropout_mults(a, mlt, r0, nr, t, TT_THREADS);
+  load_head_weights(a, L, hw, t, TT_THREADS);
   if (PHASE == 2) for (int e = t; e < nr * 16; e += TT_THREADS) lg[e] = q.lg[(long)r0 * 16 + e];
   __syncthreads();
   if (PHASE == 1) {
     // ---- classifier heads: 16 threads per sample, one per logit (emotion classes, cause, pair)
     for (int e = t; e < nr * 16; e += TT_THREADS) {
-      const int b = e >> 4, h = e & 15;
-      float s = 0.f;
-      if (h < a.EC) {
-        s = hw[o_eb + h];
-        for (int k = 0; k < D; ++k) s = fmaf(hw[h * D + k], zl[b * D2 + k] * mlt[b * D4 + k], s);
-      } else if (h == a.EC) {
-        s = hw[o_cb];
-        for (int k = 0; k < D; ++k) s = fmaf(hw[o_cw + k], zl[b * D2 + D + k] * mlt[b * D4 + D + k], s);
-      } else if (h == a.EC + 1) {
-        s = hw[o_pb];
-        for (int k = 0; k < D2; ++k) s = fmaf(hw[o_pw + k], zl[b * D2 + k] * mlt[b * D4 + D2 + k], s);
-      }
+      const float s = head_logit(a, L, hw, zl, mlt, e >> 4, e & 15);
       lg[e] = s;
       q.lg[(long)r0 * 16 + e] = s;
     }
@@ -716,53 +522,16 @@ __global__ __launch_bounds__(TT_THREADS) void tail_heads_kernel(TailTiled q) {
   float ysum = 0.f;
   for (int b = t; b < B; b += TT_THREADS) ysum += a.pair_labels[b];
   ysum = block_sum(ysum, red);                    // (its barriers also publish lg)
-  const float ntot = a.label_sum_override ? a.n_override : (float)B;
-  float ytot = ysum;
-  if (a.label_sum_override) {
-    ytot = a.label_sum_override[0];
-    for (int r = 1; r < a.label_sum_ranks; ++r) ytot += a.label_sum_override[(long)r * a.rank_stride];
-  }
-  const float pw = (ntot - ytot) / ytot;          // inf when there is no positive in the batch
+  const float pw = pair_pos_weight(a, ysum);
   if (PHASE == 1) {
     float l_emo = 0.f, l_cau = 0.f, l_pair = 0.f;
-    for (int b = t; b < nr; b += TT_THREADS) {
-      const int bg = r0 + b;
-      if (!a.emo_bce) {
-        float mx = -INFINITY;
-        for (int c = 0; c < a.EC; ++c) mx = fmaxf(mx, lg[b * 16 + c]);
-        float se = 0.f;
-        for (int c = 0; c < a.EC; ++c) se += expf(lg[b * 16 + c] - mx);
-        const float lse = mx + logf(se);
-        long lab = a.emo_labels[bg]; lab = lab < 0 ? 0 : (lab >= a.EC ? a.EC - 1 : lab);
-        l_emo += lse - lg[b * 16 + lab];
-      } else {
-        const float pe = 1.0f / (1.0f + expf(-lg[b * 16]));
-        const float te = (float)a.emo_labels[bg] * (1.f - a.ls) + a.ls;
-        l_emo += -(te * fmaxf(logf(pe), -100.f) + (1.f - te) * fmaxf(logf(1.f - pe), -100.f));
-      }
-      const float pc = 1.0f / (1.0f + expf(-lg[b * 16 + a.EC]));
-      const float tc = a.cau_labels[bg] * (1.f - a.ls) + a.ls;
-      l_cau += -(tc * fmaxf(logf(pc), -100.f) + (1.f - tc) * fmaxf(logf(1.f - pc), -100.f));
-      const float xp = lg[b * 16 + a.EC + 1];
-      const float tp = a.pair_labels[bg] * (1.f - a.ls) + a.ls;
-      const float lw = (pw - 1.f) * tp + 1.f;
-      l_pair += (1.f - tp) * xp + lw * (log1pf(expf(-fabsf(xp))) + fmaxf(-xp, 0.f));
-    }
+    for (int b = t; b < nr; b += TT_THREADS) head_row_losses(a, lg + b * 16, r0 + b, pw, l_emo, l_cau, l_pair);
     l_emo = block_sum(l_emo, red);
     l_cau = block_sum(l_cau, red);
     l_pair = block_sum(l_pair, red);
     // ---- KL (:525-534) and its direct gradient on lat
     float kle = 0.f, klc = 0.f;
-    for (int e = t; e < nr * D; e += TT_THREADS) {
-      const int b = r0 + e / D, k = e % D;
-      const float* row = a.lat + (long)b * 4 * D;
-      const float mue = row[k], lve = row[D + k], muc = row[2 * D + k], lvc = row[3 * D + k];
-      kle += -0.5f * (1.f + lve - expf(lve) - mue * mue);
-      klc += -0.5f * (1.f + lvc - expf(lvc) - muc * muc);
-      float* dl = a.dlat_direct + (long)b * 4 * D;
-      dl[k] = a.kl_w * mue / B; dl[D + k] = a.kl_w * (-0.5f) * (1.f - expf(lve)) / B;
-      dl[2 * D + k] = a.kl_w * muc / B; dl[3 * D + k] = a.kl_w * (-0.5f) * (1.f - expf(lvc)) / B;
-    }
+    for (int e = t; e < nr * D; e += TT_THREADS) kl_row(a, r0 + e / D, e % D, kle, klc);
     kle = block_sum(kle, red);
     klc = block_sum(klc, red);
     if (t == 0) {
@@ -781,96 +550,36 @@ __global__ __launch_bounds__(TT_THREADS) void tail_heads_kernel(TailTiled q) {
   kle = kle / B * a.kl_w; klc = klc / B * a.kl_w;
   const bool dead = isinf(l_pair);
   if (dead) l_pair = 0.f;
-  for (int b = t; b < nr; b += TT_THREADS) {
-    const int bg = r0 + b;
-    if (!a.emo_bce) {
-      float mx = -INFINITY;
-      for (int c = 0; c < a.EC; ++c) mx = fmaxf(mx, lg[b * 16 + c]);
-      float se = 0.f;
-      for (int c = 0; c < a.EC; ++c) se += expf(lg[b * 16 + c] - mx);
-      const float lse = mx + logf(se);
-      long lab = a.emo_labels[bg]; lab = lab < 0 ? 0 : (lab >= a.EC ? a.EC - 1 : lab);
-      for (int c = 0; c < a.EC; ++c) elog[b * 8 + c] = (expf(lg[b * 16 + c] - lse) - (c == lab ? 1.f : 0.f)) * (a.w_emo / B);
-    } else {
-      const float pe = 1.0f / (1.0f + expf(-lg[b * 16]));
-      const float te = (float)a.emo_labels[bg] * (1.f - a.ls) + a.ls;
-      const float gpe = (pe - te) / fmaxf((1.f - pe) * pe, 1e-12f);
-      elog[b * 8] = gpe * pe * (1.f - pe) * (a.w_emo / B);
-    }
-    const float pc = 1.0f / (1.0f + expf(-lg[b * 16 + a.EC]));
-    const float tc = a.cau_labels[bg] * (1.f - a.ls) + a.ls;
-    const float gp = (pc - tc) / fmaxf((1.f - pc) * pc, 1e-12f);
-    gx[b * 2] = gp * pc * (1.f - pc) * (a.w_cau / B);
-    const float xb = lg[b * 16 + a.EC + 1], tb = a.pair_labels[bg] * (1.f - a.ls) + a.ls;
-    const float lw = (pw - 1.f) * tb + 1.f;
-    const float sg = 1.0f / (1.0f + expf(-xb));
-    gx[b * 2 + 1] = dead ? 0.f : ((1.f - tb) - lw * (1.f - sg)) * (a.w_pair / B);
-  }
+  for (int b = t; b < nr; b += TT_THREADS) head_row_dlogits(a, lg + b * 16, r0 + b, pw, dead, elog + b * 8, gx + b * 2);
   __syncthreads();
   // ---- dz = d(statistic)/dz + the three heads
   for (int e = t; e < nr * D2; e += TT_THREADS) {
     const int b = e / D2, k = e - b * D2;
-    float g = hw[o_pw + k] * gx[b * 2 + 1] * mlt[b * D4 + D2 + k];
-    if (k < D) {
-      float s = 0.f;
-      for (int c = 0; c < a.EC; ++c) s = fmaf(hw[c * D + k], elog[b * 8 + c], s);
-      g += s * mlt[b * D4 + k];
-    } else {
-      g += hw[o_cw + (k - D)] * gx[b * 2] * mlt[b * D4 + k];
-    }
+    const float g = heads_dz(a, L, hw, mlt, elog, gx, b, k);
     const float g0 = a.dz_mmd ? a.dz_mmd[(long)r0 * D2 + e] : 0.f;
     a.dz[(long)r0 * D2 + e] = g0 + g;
   }
   // ---- head parameter gradients of this slab's rows: thread per parameter element, rows in order
-  float* hp = q.hpart + (long)blockIdx.x * n_hw;
-  for (int e = t; e < n_hw; e += TT_THREADS) {
-    float s = 0.f;
-    if (e < o_eb) {
-      const int c = e / D, k = e - c * D;
-      for (int b = 0; b < nr; ++b) s = fmaf(elog[b * 8 + c], zl[b * D2 + k] * mlt[b * D4 + k], s);
-    } else if (e < o_cw) {
-      const int c = e - o_eb;
-      for (int b = 0; b < nr; ++b) s += elog[b * 8 + c];
-    } else if (e < o_cb) {
-      const int k = e - o_cw;
-      for (int b = 0; b < nr; ++b) s = fmaf(gx[b * 2], zl[b * D2 + D + k] * mlt[b * D4 + D + k], s);
-    } else if (e == o_cb) {
-      for (int b = 0; b < nr; ++b) s += gx[b * 2];
-    } else if (e < o_pb) {
-      const int k = e - o_pw;
-      for (int b = 0; b < nr; ++b) s = fmaf(gx[b * 2 + 1], zl[b * D2 + k] * mlt[b * D4 + D2 + k], s);
-    } else {
-      for (int b = 0; b < nr; ++b) s += gx[b * 2 + 1];
-    }
-    hp[e] = s;
-  }
+  float* hp = q.hpart + (long)blockIdx.x * L.n;
+  for (int e = t; e < L.n; e += TT_THREADS) hp[e] = head_param_grad(a, L, zl, mlt, elog, gx, e, nr);
   if (blockIdx.x == 0 && t == 0) {
     float mmd = 0.f, dis_term = 0.f;
-    if (a.dis_mode == 0) {          // partial block sums in fixed order, double accumulation (tail_core_kernel's mmd_part branch)
-      const int nm = a.z_global ? a.n_global : B;
-      double s11 = 0.0, s22 = 0.0, s12 = 0.0;
-      for (int p = 0; p < a.mmd_nblk; ++p) { s11 += a.mmd_part[p * 4]; s22 += a.mmd_part[p * 4 + 1]; s12 += a.mmd_part[p * 4 + 2]; }
-      const double b00 = 1.0 / ((double)nm * (nm - 1)), b01 = -1.0 / ((double)nm * nm);
-      mmd = (float)(2.0 * b01 * s12 + b00 * s11 + b00 * s22);
+    if (a.dis_mode == 0) {
+      mmd = mmd_from_partials(a, a.z_global ? a.n_global : B);
       dis_term = -a.w_mmd * mmd;
     }
-    a.terms[1] = mmd; a.terms[2] = l_emo; a.terms[3] = l_cau; a.terms[4] = l_pair; a.terms[5] = kle; a.terms[6] = klc;
-    a.terms[0] = dis_term + a.w_emo * l_emo + a.w_cau * l_cau + a.w_pair * l_pair + kle + klc;
-    a.pair_dead[0] = dead ? 1.f : 0.f;
+    write_terms(a, mmd, dis_term, l_emo, l_cau, l_pair, kle, klc, dead);
   }
 }
 
 // head parameter gradients = the slabs' partials added in slab order
 __global__ __launch_bounds__(TT_THREADS) void tail_head_grads_kernel(TailTiled q, int nslab) {
   const TailCore& a = q.c;
-  const int D = a.D, D2 = 2 * a.D;
-  const int o_eb = a.EC * D, o_cw = o_eb + a.EC, o_cb = o_cw + D, o_pw = o_cb + 1, o_pb = o_pw + D2, n_hw = o_pb + 1;
-  for (int e = threadIdx.x; e < n_hw; e += TT_THREADS) {
+  const HeadLayout L(a.EC, a.D);
+  for (int e = threadIdx.x; e < L.n; e += TT_THREADS) {
     float s = 0.f;
-    for (int p = 0; p < nslab; ++p) s += q.hpart[(long)p * n_hw + e];
-    float* dst = e < o_eb ? a.d_emo_w + e : e < o_cw ? a.d_emo_b + (e - o_eb) : e < o_cb ? a.d_cau_w + (e - o_cw) : e < o_pw ? a.d_cau_b
-               : e < o_pb ? a.d_pair_w + (e - o_pw) : a.d_pair_b;
-    *dst = s;
+    for (int p = 0; p < nslab; ++p) s += q.hpart[(long)p * L.n + e];
+    *head_grad_dst(a, L, e) = s;
   }
 }
 
@@ -925,10 +634,7 @@ __global__ __launch_bounds__(DEC_J * DEC_MAXG) void decoder_tiled_kernel(DecArgs
             float le = 0.f, dt = 0.f;
             if (live) {
               const float lp = dec_logit<CD2>(wr, zl + lb * D2, D2, bias) - a.rowstat[(t0 + lb) * 4] - a.rowstat[(t0 + lb) * 4 + 1];
-              const float p = expf(lp);
-              const float tg = bw[u] * (1.f - a.ls) + a.ls / a.V;
-              le = -(tg * fmaxf(lp, -100.f) + (1.f - tg) * fmaxf(log1pf(-p), -100.f));
-              dt = p * ((p - tg) / fmaxf((1.f - p) * p, 1e-12f));
+              dec_loss_dot(lp, dec_target(a, bw[u]), le, dt);
             }
             tile[lb * DEC_J + tj] = le; tile2[lb * DEC_J + tj] = dt;
           }
@@ -961,8 +667,7 @@ __global__ __launch_bounds__(DEC_J * DEC_MAXG) void decoder_tiled_kernel(DecArgs
             if (live) {
               const float lp = dec_logit<CD2>(wr, zl + lb * D2, D2, bias) - a.rowstat[(t0 + lb) * 4] - a.rowstat[(t0 + lb) * 4 + 1];
               const float p = expf(lp);
-              const float tg = bw[u] * (1.f - a.ls) + a.ls / a.V;
-              const float gp = (p - tg) / fmaxf((1.f - p) * p, 1e-12f);
+              const float gp = bce_dprob(p, dec_target(a, bw[u]));
               gg = p * (gp - a.rowstat[(t0 + lb) * 4 + 2]) * a.gscale;
               _Pragma("unroll") for (int k = 0; k < D2; ++k) dwr[k] = fmaf(gg, zl[lb * D2 + k], dwr[k]);
               dbj += gg;
@@ -1087,7 +792,7 @@ extern "C" int carel_pair_probs(const void* lat, const void* eps_e, const void* 
 // ---- the two LDS plans of carel_tail_losses (its batch limit), shared with carel_tail_batch_limit
 // loss kernel (one workgroup): the whole batch's z, dz, dropout multipliers, logits, dlogits and the MMD / HSIC rows (nm per side)
 static size_t tail_core_lds_bytes(int B, int D, int EC, int nm) {
-  const int n_hw = EC * D + EC + D + 1 + 2 * D + 1;
+  const int n_hw = HeadLayout(EC, D).n;
   return sizeof(float) * (64 + 64 + (size_t)2 * B * 2 * D + (size_t)B * 8 + (size_t)B * 2 + (size_t)B * 4 * D + (size_t)B * 16 +
                           ((n_hw + 3) & ~3) + ((2 * nm + 3) & ~3) + (size_t)2 * nm * (D | 1) + 2 * (size_t)B);
 }
@@ -1109,6 +814,61 @@ extern "C" int32_t carel_tail_batch_limit(int32_t ec_dim, int32_t e_classes) {
   int B = 1;       // both plans grow with the batch: the largest accepted one is the last before the first refusal
   while (tail_core_lds_bytes(B + 1, ec_dim, e_classes, B + 1) <= TAIL_LDS_MAX && tail_decoder_plan(B + 1, ec_dim).ldsmax <= TAIL_LDS_MAX) ++B;
   return B >= 2 ? B : 0;
+}
+
+// ---- launches common to carel_tail_losses and carel_tail_losses_tiled
+// the global-batch MMD kernel on nm samples per side: block partials -> w.mmd_part, d/dz of the local rows -> w.dz_mmd
+static int launch_mmd_global(TailCore& c, const TailWork& w, const float* zg, int nm, int rank_stride, int row_offset, hipStream_t stream) {
+  MmdGlobalArgs g;
+  g.zg = zg; g.n = nm; g.B = c.B; g.D = c.D; g.rank_stride = rank_stride; g.row_offset = row_offset;
+  g.alpha = c.alpha; g.eps = c.mmd_eps; g.gscale = -c.w_mmd * c.mmd_grad_scale; g.part = w.mmd_part; g.dz = w.dz_mmd;
+  const int nblk = (2 * nm + 31) / 32;
+  if (c.D == 24) hipLaunchKernelGGL(mmd_global_kernel<24>, dim3(nblk), dim3(256), 0, stream, g);
+  else hipLaunchKernelGGL(mmd_global_kernel<32>, dim3(nblk), dim3(256), 0, stream, g);
+  if (int rc = check_launch("mmd_global_kernel")) return rc;
+  c.mmd_part = w.mmd_part; c.mmd_nblk = nblk; c.dz_mmd = w.dz_mmd;
+  return CAREL_OK;
+}
+
+static DecArgs dec_args(const carel_tail_args* a, const TailWork& w) {
+  DecArgs d;
+  d.B = a->batch; d.D2 = 2 * a->ec_dim; d.V = a->bow_dim; d.z = (const float*)a->z; d.w = (const float*)a->dec_w; d.b = (const float*)a->dec_b;
+  d.bow = (const float*)a->bow; d.ls = a->label_smoothing; d.part = w.part; d.rowstat = w.rowstat; d.dz_part = w.dz_part;
+  d.dw = (float*)a->d_dec_w; d.db = (float*)a->d_dec_b; d.gscale = 1.0f / ((float)a->batch * (float)a->bow_dim);
+  return d;
+}
+
+// the two decoder families: [0] the compile-time width 48 (ec_dim 24), [1] a run-time width; passes 1..3 in each
+static void (*const DEC_WG[2][3])(DecArgs) = {{decoder_kernel<1, 48>, decoder_kernel<2, 48>, decoder_kernel<3, 48>},
+                                              {decoder_kernel<1, 0>, decoder_kernel<2, 0>, decoder_kernel<3, 0>}};
+static void (*const DEC_TILED[2][3])(DecArgs, int) = {{decoder_tiled_kernel<1, 48>, decoder_tiled_kernel<2, 48>, decoder_tiled_kernel<3, 48>},
+                                                      {decoder_tiled_kernel<1, 0>, decoder_tiled_kernel<2, 0>, decoder_tiled_kernel<3, 0>}};
+// the three passes with the two combines between them.  grid12: passes 1 and 2, grid3: pass 3; lds: per pass; x: the tiled family's TB
+template <typename F, typename... X>
+static void launch_decoder(F* const (&K)[2][3], const DecArgs& d, dim3 grid12, dim3 grid3, int threads, const size_t (&lds)[3],
+                           hipStream_t stream, X... x) {
+  F* const (&k)[3] = K[d.D2 == 48 ? 0 : 1];
+  const int chunks = (d.V + DEC_J - 1) / DEC_J;
+  hipLaunchKernelGGL(k[0], grid12, dim3(threads), lds[0], stream, d, x...);
+  hipLaunchKernelGGL(decoder_combine_kernel, dim3((d.B + 3) / 4), dim3(256), 0, stream, (const float*)d.part, chunks, d.B, 1, d.rowstat);
+  hipLaunchKernelGGL(k[1], grid12, dim3(threads), lds[1], stream, d, x...);
+  hipLaunchKernelGGL(decoder_combine_kernel, dim3((d.B + 3) / 4), dim3(256), 0, stream, (const float*)d.part, chunks, d.B, 2, d.rowstat);
+  hipLaunchKernelGGL(k[2], grid3, dim3(threads), lds[2], stream, d, x...);
+}
+
+// sum the decoder's per-chunk dz partials into slot 0 (in place is safe: block c only reads column c of every part)
+static void launch_dz_reduce(const carel_tail_args* a, const TailWork& w, hipStream_t stream) {
+  const int n = a->batch * 2 * a->ec_dim;
+  hipLaunchKernelGGL(reduce_parts16_kernel, dim3((n + 15) / 16), dim3(256), 0, stream, (const float*)w.dz_part, w.dz_part, n, (a->bow_dim + DEC_J - 1) / DEC_J);
+}
+// where the loss kernels and the decoder meet: terms[7..8] (reads terms[0] of the loss kernel), and d(loss)/d lat, unscaled (grad_output
+// is applied in carel_tail_backward)
+static int launch_tail_close(const carel_tail_args* a, const TailWork& w, float inv_bv, hipStream_t stream) {
+  const int B = a->batch, D = a->ec_dim;
+  hipLaunchKernelGGL(decoder_total_kernel, dim3(1), dim3(256), 0, stream, (const float*)w.rowstat, B, inv_bv, (float*)a->terms);
+  hipLaunchKernelGGL(tail_dlat_kernel, dim3((B * 2 * D + 255) / 256), dim3(256), 0, stream, (const float*)w.dz_core, (const float*)w.dz_part,
+                     1, (const float*)w.dlat_direct, (const float*)a->lat, (const float*)a->eps_e, (const float*)a->eps_c, B, D, 1.0f, w.dlat);
+  return check_launch("tail_dlat_kernel");
 }
 
 // Argument checks and the loss kernel's arguments, common to carel_tail_losses and carel_tail_losses_tiled (`who` names the caller
@@ -1175,14 +935,12 @@ extern "C" int carel_tail_losses(const carel_tail_args* a, void* stream_) {
   // kernels keep the whole batch in the 160 KB LDS of one CU.
   const int chunks = (V + DEC_J - 1) / DEC_J;
   const DecPlan dp = tail_decoder_plan(B, D);
-  const int G = dp.G;
-  const size_t lds1 = dp.lds1, lds2 = dp.lds2, lds3 = dp.lds3, ldsmax = dp.ldsmax;
-  if (ldsmax > TAIL_LDS_MAX) return set_error(CAREL_ERR_SHAPE, "carel_tail_losses: batch too large for the decoder kernel (%zu B LDS)", ldsmax);
-  if (ldsmax > 64 * 1024) {
+  if (dp.ldsmax > TAIL_LDS_MAX) return set_error(CAREL_ERR_SHAPE, "carel_tail_losses: batch too large for the decoder kernel (%zu B LDS)", dp.ldsmax);
+  if (dp.ldsmax > 64 * 1024) {
     hipError_t e = hipSuccess;
-    const void* fns[6] = {(const void*)decoder_kernel<1, 48>, (const void*)decoder_kernel<2, 48>, (const void*)decoder_kernel<3, 48>,
-                          (const void*)decoder_kernel<1, 0>, (const void*)decoder_kernel<2, 0>, (const void*)decoder_kernel<3, 0>};
-    for (int i = 0; i < 6 && e == hipSuccess; ++i) e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsmax);
+    for (auto& family : DEC_WG)
+      for (auto kernel : family)
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dp.ldsmax);
     if (e != hipSuccess) return set_error(CAREL_ERR_HIP, "carel_tail_losses: hipFuncSetAttribute: %s", hipGetErrorString(e));
   }
   c.mmd_part = nullptr; c.mmd_nblk = 0; c.dz_mmd = nullptr;
@@ -1215,44 +973,20 @@ extern "C" int carel_tail_losses(const carel_tail_args* a, void* stream_) {
     }
   }
   if (c.z_global && c.dis_mode == 0) {
-    MmdGlobalArgs g;
-    g.zg = c.z_global; g.n = c.n_global; g.B = B; g.D = D; g.rank_stride = c.rank_stride; g.row_offset = c.row_offset;
-    g.alpha = c.alpha; g.eps = c.mmd_eps; g.gscale = -c.w_mmd * c.mmd_grad_scale; g.part = w.mmd_part; g.dz = w.dz_mmd;
-    const int nblk = (2 * c.n_global + 31) / 32;
-    if (D == 24) hipLaunchKernelGGL(mmd_global_kernel<24>, dim3(nblk), dim3(256), 0, core_stream, g);
-    else hipLaunchKernelGGL(mmd_global_kernel<32>, dim3(nblk), dim3(256), 0, core_stream, g);
-    if ((rc = check_launch("mmd_global_kernel"))) return join_on_error(rc);
-    c.mmd_part = w.mmd_part; c.mmd_nblk = nblk; c.dz_mmd = w.dz_mmd;
+    if ((rc = launch_mmd_global(c, w, c.z_global, c.n_global, c.rank_stride, c.row_offset, core_stream))) return join_on_error(rc);
   }
   c.prof = g_tail_prof;
   hipLaunchKernelGGL(tail_core_kernel, dim3(1), dim3(1024), lds, core_stream, c);
   if ((rc = check_launch("tail_core_kernel"))) return join_on_error(rc);
   if (tev && hipEventRecord(tev->join, core_stream) != hipSuccess) return join_on_error(set_error(CAREL_ERR_HIP, "carel_tail_losses: event record failed"));
 
-  DecArgs d;
-  d.B = B; d.D2 = 2 * D; d.V = V; d.z = (const float*)a->z; d.w = (const float*)a->dec_w; d.b = (const float*)a->dec_b;
-  d.bow = (const float*)a->bow; d.ls = a->label_smoothing; d.part = w.part; d.rowstat = w.rowstat; d.dz_part = w.dz_part;
-  d.dw = (float*)a->d_dec_w; d.db = (float*)a->d_dec_b; d.gscale = 1.0f / ((float)B * (float)V);
-#define DEC_LAUNCH(PASS, LDS)                                                                              \
-  do {                                                                                                  \
-    if (2 * D == 48) hipLaunchKernelGGL((decoder_kernel<PASS, 48>), dim3(chunks), dim3(DEC_J * G), LDS, stream, d); \
-    else hipLaunchKernelGGL((decoder_kernel<PASS, 0>), dim3(chunks), dim3(DEC_J * G), LDS, stream, d);      \
-  } while (0)
-  DEC_LAUNCH(1, lds1);
-  hipLaunchKernelGGL(decoder_combine_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, (const float*)w.part, chunks, B, 1, w.rowstat);
-  DEC_LAUNCH(2, lds2);
-  hipLaunchKernelGGL(decoder_combine_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, (const float*)w.part, chunks, B, 2, w.rowstat);
-  DEC_LAUNCH(3, lds3);
-#undef DEC_LAUNCH
+  const DecArgs d = dec_args(a, w);
+  const size_t dec_lds[3] = {dp.lds1, dp.lds2, dp.lds3};
+  launch_decoder(DEC_WG, d, dim3(chunks), dim3(chunks), DEC_J * dp.G, dec_lds, stream);
   if ((rc = check_launch("decoder kernels"))) return join_on_error(rc);
-  // d(loss)/d lat, unscaled (grad_output is applied in carel_tail_backward)
-  // sum the decoder's per-chunk dz partials into slot 0 (in place is safe: block c only reads column c of every part)
-  hipLaunchKernelGGL(reduce_parts16_kernel, dim3((B * 2 * D + 15) / 16), dim3(256), 0, stream, (const float*)w.dz_part, w.dz_part, B * 2 * D, chunks);
+  launch_dz_reduce(a, w, stream);
   if (tev && hipStreamWaitEvent(stream, tev->join, 0) != hipSuccess) return join_on_error(set_error(CAREL_ERR_HIP, "carel_tail_losses: event join failed"));
-  hipLaunchKernelGGL(decoder_total_kernel, dim3(1), dim3(256), 0, stream, (const float*)w.rowstat, B, d.gscale, (float*)a->terms);   // reads terms[0] of the loss kernel
-  hipLaunchKernelGGL(tail_dlat_kernel, dim3((B * 2 * D + 255) / 256), dim3(256), 0, stream, (const float*)w.dz_core, (const float*)w.dz_part,
-                     1, (const float*)w.dlat_direct, (const float*)a->lat, (const float*)a->eps_e, (const float*)a->eps_c, B, D, 1.0f, w.dlat);
-  return check_launch("tail_dlat_kernel");
+  return launch_tail_close(a, w, d.gscale, stream);
 }
 
 // The batch-tiled form of carel_tail_losses: same contract, same outputs, same workspace carve, same dropout streams, the same
@@ -1276,7 +1010,7 @@ extern "C" int carel_tail_losses_tiled(const carel_tail_args* a, void* stream_) 
   const int nblk = (2 * nm + 31) / 32;
   if (c.dis_mode == 0 && nblk > MMD_MAX_BLOCKS) return set_error(CAREL_ERR_SHAPE, "%s: global batch too large for the MMD partial buffer", who);
   const int nslab = (B + TT_R - 1) / TT_R;
-  const int n_hw = a->e_classes * D + a->e_classes + D + 1 + 2 * D + 1;
+  const int n_hw = HeadLayout(a->e_classes, D).n;
   const size_t lds_h = sizeof(float) * (64 + (size_t)TT_R * (2 * D + 4 * D + 16 + 8 + 2) + ((n_hw + 3) & ~3));
   const int D2 = 2 * D, chunks = (V + DEC_J - 1) / DEC_J;
   auto dec_lds = [&](int tb, int tiles) { return sizeof(float) * ((size_t)tb * D2 + ((DEC_J * (D2 + 1) + 3) & ~3) + (size_t)tiles * tb * DEC_J); };
@@ -1288,41 +1022,21 @@ extern "C" int carel_tail_losses_tiled(const carel_tail_args* a, void* stream_) 
 
   hipLaunchKernelGGL(sample_z_kernel, dim3((B * 2 * D + 255) / 256), dim3(256), 0, stream, c.lat, c.eps_e, c.eps_c, B, D, c.z);
   if (c.dis_mode == 0) {
-    MmdGlobalArgs g;
-    g.zg = c.z_global ? c.z_global : (const float*)c.z; g.n = nm; g.B = B; g.D = D;
-    g.rank_stride = c.z_global ? c.rank_stride : B * 2 * D; g.row_offset = c.z_global ? c.row_offset : 0;
-    g.alpha = c.alpha; g.eps = c.mmd_eps; g.gscale = -c.w_mmd * c.mmd_grad_scale; g.part = w.mmd_part; g.dz = w.dz_mmd;
-    if (D == 24) hipLaunchKernelGGL(mmd_global_kernel<24>, dim3(nblk), dim3(256), 0, stream, g);
-    else hipLaunchKernelGGL(mmd_global_kernel<32>, dim3(nblk), dim3(256), 0, stream, g);
-    if ((rc = check_launch("mmd_global_kernel"))) return rc;
-    c.mmd_part = w.mmd_part; c.mmd_nblk = nblk; c.dz_mmd = w.dz_mmd;
+    rc = c.z_global ? launch_mmd_global(c, w, c.z_global, nm, c.rank_stride, c.row_offset, stream)
+                    : launch_mmd_global(c, w, c.z, nm, B * 2 * D, 0, stream);          // on the batch's own z
+    if (rc) return rc;
   }
   hipLaunchKernelGGL(tail_heads_kernel<1>, dim3(nslab), dim3(TT_THREADS), lds_h, stream, q);
   hipLaunchKernelGGL(tail_heads_kernel<2>, dim3(nslab), dim3(TT_THREADS), lds_h, stream, q);
   hipLaunchKernelGGL(tail_head_grads_kernel, dim3(1), dim3(TT_THREADS), 0, stream, q, nslab);
   if ((rc = check_launch("tail_heads_kernel"))) return rc;
 
-  DecArgs d;
-  d.B = B; d.D2 = D2; d.V = V; d.z = (const float*)a->z; d.w = (const float*)a->dec_w; d.b = (const float*)a->dec_b;
-  d.bow = (const float*)a->bow; d.ls = a->label_smoothing; d.part = w.part; d.rowstat = w.rowstat; d.dz_part = w.dz_part;
-  d.dw = (float*)a->d_dec_w; d.db = (float*)a->d_dec_b; d.gscale = 1.0f / ((float)B * (float)V);
-#define DEC_TILED_LAUNCH(PASS, GRID, LDS)                                                                                         \
-  do {                                                                                                                         \
-    if (D2 == 48) hipLaunchKernelGGL((decoder_tiled_kernel<PASS, 48>), GRID, dim3(DEC_J * DEC_MAXG), LDS, stream, d, TB);          \
-    else hipLaunchKernelGGL((decoder_tiled_kernel<PASS, 0>), GRID, dim3(DEC_J * DEC_MAXG), LDS, stream, d, TB);                    \
-  } while (0)
-  DEC_TILED_LAUNCH(1, dim3(chunks, ntile), dec_lds(TB, 1));
-  hipLaunchKernelGGL(decoder_combine_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, (const float*)w.part, chunks, B, 1, w.rowstat);
-  DEC_TILED_LAUNCH(2, dim3(chunks, ntile), dec_lds(TB, 2));
-  hipLaunchKernelGGL(decoder_combine_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, (const float*)w.part, chunks, B, 2, w.rowstat);
-  DEC_TILED_LAUNCH(3, dim3(chunks), dec_lds(TB, 1));
-#undef DEC_TILED_LAUNCH
+  const DecArgs d = dec_args(a, w);
+  const size_t lds_d[3] = {dec_lds(TB, 1), dec_lds(TB, 2), dec_lds(TB, 1)};
+  launch_decoder(DEC_TILED, d, dim3(chunks, ntile), dim3(chunks), DEC_J * DEC_MAXG, lds_d, stream, TB);
   if ((rc = check_launch("decoder kernels (tiled)"))) return rc;
-  hipLaunchKernelGGL(reduce_parts16_kernel, dim3((B * 2 * D + 15) / 16), dim3(256), 0, stream, (const float*)w.dz_part, w.dz_part, B * 2 * D, chunks);
-  hipLaunchKernelGGL(decoder_total_kernel, dim3(1), dim3(256), 0, stream, (const float*)w.rowstat, B, d.gscale, (float*)a->terms);
-  hipLaunchKernelGGL(tail_dlat_kernel, dim3((B * 2 * D + 255) / 256), dim3(256), 0, stream, (const float*)w.dz_core, (const float*)w.dz_part,
-                     1, (const float*)w.dlat_direct, (const float*)a->lat, (const float*)a->eps_e, (const float*)a->eps_c, B, D, 1.0f, w.dlat);
-  return check_launch("tail_dlat_kernel");
+  launch_dz_reduce(a, w, stream);
+  return launch_tail_close(a, w, d.gscale, stream);
 }
 
 // Back-propagate d(loss)/d lat through the latent heads and the pooler into the encoder output.
