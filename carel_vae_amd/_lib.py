@@ -180,6 +180,18 @@ class GanArgs(C.Structure):
                 ("g_ent_w", C.c_void_p * 2), ("g_ent_b", C.c_void_p * 2)]
 
 
+class TripletArgs(C.Structure):
+    """carel_triplet_args (include/carel_hip.h)."""
+    _fields_ = [("emb", C.c_void_p), ("labels", C.c_void_p), ("batch", C.c_int32), ("hidden", C.c_int32), ("mode", C.c_int32),
+                ("distance", C.c_int32), ("margin", C.c_float), ("loss_out", C.c_void_p), ("demb", C.c_void_p), ("stats_out", C.c_void_p),
+                ("work", C.c_void_p)]
+
+
+TRIPLET_SEMIHARD, TRIPLET_ALL, TRIPLET_HARD, TRIPLET_HARD_SOFT = range(4)
+TRIPLET_EUCLIDEAN, TRIPLET_DOT = range(2)
+TRIPLET_MAX_BATCH = 512
+
+
 class EnTailArgs(C.Structure):
     """carel_en_tail_args (include/carel_hip.h)."""
     _fields_ = [("batch", C.c_int32), ("seq_len", C.c_int32), ("hidden", C.c_int32), ("ec_dim", C.c_int32), ("con_dim", C.c_int32),
@@ -245,6 +257,8 @@ SIGNATURES = {
     "carel_mean_pool_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "carel_mean_pool_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "carel_triplet_semihard": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "carel_triplet_workspace_floats": (C.c_int64, [C.c_int32]),
+    "carel_triplet_loss": (C.c_int, [C.POINTER(TripletArgs), C.c_void_p]),
     "carel_grad_norm_clip": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "carel_l2_normalize_fwd": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "carel_l2_normalize_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

@@ -7,6 +7,13 @@ mean pooling + Normalize) -- the names the scripts use from the third-party `sen
     train_loss = losses.BatchSemiHardTripletLoss(model=model, margin=4.45)        (:78)
     model.fit(train_objectives=[(train_dataloader, train_loss)], epochs=..., warmup_steps=..., output_path=...)   (:84-87)
 
+`losses` holds the package's whole batch triplet family with its constructor shapes -- BatchSemiHardTripletLoss, BatchAllTripletLoss
+(chi_sentence_transformer_old.py:33), BatchHardTripletLoss, BatchHardSoftMarginTripletLoss, and BatchHardTripletLossDistanceFunction
+(eucledian_distance / cosine_distance, used as selectors) -- for batches of up to 512 sentences: carel_triplet_loss
+(csrc/triplet_family.hip: distance tiles, one mining workgroup per anchor, a finish and a gradient launch; the cosine metric is its
+"one minus dot product" between carel_l2_normalize_fwd and _bwd).  Semi-hard with the Euclidean metric on at most 64 sentences keeps
+the one-workgroup kernel of csrc/triplet.hip and its bits.  tests/triplet_restate.py restates the four losses in float64.
+
 What runs where: the encoder is the same bf16-MFMA BERT stack as the VAE path (carel_encoder_forward / _backward_layer, every
 token of the last layer kept: cls_only_last off); mean pooling, the batch-semi-hard triplet loss (forward + gradient), the
 global gradient norm and AdamW (decoupled weight decay on the weight matrices, clip coefficient read from device memory) are
@@ -84,24 +91,160 @@ class _TripletFn(torch.autograd.Function):
         return demb * g, None, None
 
 
+class _TripletFamilyFn(torch.autograd.Function):
+    """carel_triplet_loss (csrc/triplet_family.hip): any of the four batch triplet losses on up to 512 sentences.  The cosine distance is
+    the kernel's "one minus dot product" on rows normalised by carel_l2_normalize_fwd, and the gradient goes back through
+    carel_l2_normalize_bwd: both in forward (for upstream gradient 1), so that backward is one scaling."""
+
+    @staticmethod
+    def forward(ctx, emb, labels, mode, cosine, margin, work):
+        lib = L.load()
+        emb = emb.contiguous().float()
+        B, hidden = emb.shape
+        loss = torch.empty(1, device=emb.device, dtype=torch.float32)
+        demb = torch.empty_like(emb)
+        x = emb
+        if cosine:
+            x, norm = torch.empty_like(emb), torch.empty(B, device=emb.device, dtype=torch.float32)
+            L.check(lib.carel_l2_normalize_fwd(emb.data_ptr(), B, hidden, x.data_ptr(), norm.data_ptr(), L.current_stream()), "carel_l2_normalize_fwd")
+        a = L.TripletArgs()
+        a.emb, a.labels, a.batch, a.hidden = x.data_ptr(), labels.data_ptr(), B, hidden
+        a.mode, a.distance, a.margin = int(mode), (L.TRIPLET_DOT if cosine else L.TRIPLET_EUCLIDEAN), float(margin)
+        a.loss_out, a.demb, a.work = loss.data_ptr(), demb.data_ptr(), work.data_ptr()
+        L.check(lib.carel_triplet_loss(C.byref(a), L.current_stream()), "carel_triplet_loss")
+        if cosine:
+            dx = torch.empty_like(emb)
+            L.check(lib.carel_l2_normalize_bwd(demb.data_ptr(), x.data_ptr(), norm.data_ptr(), B, hidden, dx.data_ptr(), L.current_stream()),
+                    "carel_l2_normalize_bwd")
+            demb = dx
+        ctx.save_for_backward(demb)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        demb, = ctx.saved_tensors
+        return demb * g, None, None, None, None, None
+
+
+class BatchHardTripletLossDistanceFunction:
+    """losses.BatchHardTripletLossDistanceFunction: the two metrics of the batch triplet losses, under the package's names (its
+    spelling included).  Here they are SELECTORS: pass one as `distance_metric`; the distance matrix itself is computed inside the
+    HIP loss kernels, so calling one is an error, and so is any other callable as a metric."""
+
+    @staticmethod
+    def eucledian_distance(embeddings, squared=False):
+        raise L.CarelError("BatchHardTripletLossDistanceFunction.eucledian_distance selects the metric of a batch triplet loss; the distances "
+                           "are computed by the loss's HIP kernels, not here")
+
+    @staticmethod
+    def cosine_distance(embeddings):
+        raise L.CarelError("BatchHardTripletLossDistanceFunction.cosine_distance selects the metric of a batch triplet loss; the distances are "
+                           "computed by the loss's HIP kernels, not here")
+
+
+class _BatchTripletLoss(nn.Module):
+    """What the four batch triplet losses share: the metric selector, the checks and the workspace (cached per batch size)."""
+
+    MAX_BATCH = L.TRIPLET_MAX_BATCH
+
+    def __init__(self, model, distance_metric, margin):
+        super().__init__()
+        F = BatchHardTripletLossDistanceFunction
+        if distance_metric is F.eucledian_distance:
+            self._cosine = False
+        elif distance_metric is F.cosine_distance:
+            self._cosine = True
+        else:
+            raise L.CarelError("%s: distance_metric must be BatchHardTripletLossDistanceFunction.eucledian_distance or .cosine_distance "
+                               "(the metrics the HIP kernels compute), got %r" % (type(self).__name__, distance_metric))
+        self.sentence_embedder, self.distance_metric, self.triplet_margin = model, distance_metric, float(margin)
+        self._work = {}
+
+    def forward(self, sentence_features, labels):
+        rep = self.sentence_embedder(sentence_features[0])["sentence_embedding"]
+        return self._loss(labels, rep)
+
+    def _check(self, labels, embeddings):
+        if embeddings.dim() != 2:
+            raise L.CarelError("%s: embeddings must be [sentences, hidden]" % type(self).__name__)
+        if embeddings.shape[0] > self.MAX_BATCH:
+            raise L.CarelError("%s: %d sentences in one batch; at most %d are supported" % (type(self).__name__, embeddings.shape[0], self.MAX_BATCH))
+        if labels.numel() != embeddings.shape[0]:          # the kernels read labels[0 .. sentences)
+            raise L.CarelError("%s: %d labels for %d sentences; one integer label per sentence is needed" % (
+                type(self).__name__, labels.numel(), embeddings.shape[0]))
+        if not embeddings.is_cuda:
+            raise L.CarelError("%s: the embeddings are on the CPU; the loss runs as HIP kernels only (no CPU fallback)" % type(self).__name__)
+
+    def _loss(self, labels, embeddings):
+        self._check(labels, embeddings)
+        B = embeddings.shape[0]
+        key = (B, embeddings.device)
+        work = self._work.get(key)
+        if work is None:
+            work = self._work[key] = torch.empty(L.load().carel_triplet_workspace_floats(B), device=embeddings.device, dtype=torch.float32)
+        lab = labels.to(embeddings.device, torch.int32).reshape(-1).contiguous()
+        return _TripletFamilyFn.apply(embeddings, lab, self.MODE, self._cosine, self.triplet_margin, work)
+
+
 class _Losses:
-    class BatchSemiHardTripletLoss(nn.Module):
-        """losses.BatchSemiHardTripletLoss(model, margin=5) with the package's default Euclidean distance.
-        forward(sentence_features, labels) as the package calls it from fit(); labels: integer class per sentence."""
+    BatchHardTripletLossDistanceFunction = BatchHardTripletLossDistanceFunction
 
-        def __init__(self, model, margin=5.0):
-            super().__init__()
-            self.sentence_embedder, self.triplet_margin = model, float(margin)
+    class BatchSemiHardTripletLoss(_BatchTripletLoss):
+        """losses.BatchSemiHardTripletLoss(model, margin=5); distance_metric (keyword): the package's default Euclidean distance or
+        cosine_distance.  forward(sentence_features, labels) as the package calls it from fit(); labels: integer class per sentence.
+        Euclidean batches of up to 64 sentences run on the one-workgroup kernel carel_triplet_semihard, everything else (up to 512) on
+        carel_triplet_loss."""
 
-        def forward(self, sentence_features, labels):
-            rep = self.sentence_embedder(sentence_features[0])["sentence_embedding"]
-            return self.batch_semi_hard_triplet_loss(labels, rep)
+        MODE = L.TRIPLET_SEMIHARD
 
-        def batch_semi_hard_triplet_loss(self, labels, embeddings):
-            if embeddings.shape[0] > 64:
-                raise L.CarelError("BatchSemiHardTripletLoss: at most 64 sentences per batch (the reference uses 16)")
+        def __init__(self, model, margin=5.0, *, distance_metric=BatchHardTripletLossDistanceFunction.eucledian_distance):
+            super().__init__(model, distance_metric, margin)
+
+        def _loss(self, labels, embeddings):
+            self._check(labels, embeddings)
+            if self._cosine or embeddings.shape[0] > 64:
+                return super()._loss(labels, embeddings)
             lab = labels.to(embeddings.device, torch.int32).reshape(-1).contiguous()
             return _TripletFn.apply(embeddings, lab, self.triplet_margin)
+
+        def batch_semi_hard_triplet_loss(self, labels, embeddings):
+            return self._loss(labels, embeddings)
+
+    class BatchAllTripletLoss(_BatchTripletLoss):
+        """losses.BatchAllTripletLoss(model, distance_metric=eucledian_distance, margin=5): every valid (anchor, positive, negative),
+        averaged over the triplets whose hinge is positive (chi_sentence_transformer_old.py:33)."""
+
+        MODE = L.TRIPLET_ALL
+
+        def __init__(self, model, distance_metric=BatchHardTripletLossDistanceFunction.eucledian_distance, margin=5.0):
+            super().__init__(model, distance_metric, margin)
+
+        def batch_all_triplet_loss(self, labels, embeddings):
+            return self._loss(labels, embeddings)
+
+    class BatchHardTripletLoss(_BatchTripletLoss):
+        """losses.BatchHardTripletLoss(model, distance_metric=eucledian_distance, margin=5): per anchor the farthest positive against the
+        nearest negative."""
+
+        MODE = L.TRIPLET_HARD
+
+        def __init__(self, model, distance_metric=BatchHardTripletLossDistanceFunction.eucledian_distance, margin=5.0):
+            super().__init__(model, distance_metric, margin)
+
+        def batch_hard_triplet_loss(self, labels, embeddings):
+            return self._loss(labels, embeddings)
+
+    class BatchHardSoftMarginTripletLoss(_BatchTripletLoss):
+        """losses.BatchHardSoftMarginTripletLoss(model, distance_metric=eucledian_distance): batch-hard mining with log1p(exp(hp - hn))
+        (a stable softplus) in place of the hinge; no margin."""
+
+        MODE = L.TRIPLET_HARD_SOFT
+
+        def __init__(self, model, distance_metric=BatchHardTripletLossDistanceFunction.eucledian_distance):
+            super().__init__(model, distance_metric, 0.0)
+
+        def batch_hard_triplet_soft_margin_loss(self, labels, embeddings):
+            return self._loss(labels, embeddings)
 
 
 losses = _Losses

@@ -670,6 +670,43 @@ int carel_l2_normalize_fwd(const void* x_f32, int32_t rows, int32_t hidden, void
 int carel_l2_normalize_bwd(const void* g_f32, const void* y_f32, const void* norm_f32, int32_t rows, int32_t hidden, void* dx_f32, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The batch triplet loss family of `sentence_transformers` (losses.BatchSemiHardTripletLoss, BatchAllTripletLoss -- the loss of
+ * chi_sentence_transformer_old.py:33 --, BatchHardTripletLoss, BatchHardSoftMarginTripletLoss) for 1 <= batch <= 512: forward and
+ * (demb != NULL) the gradient w.r.t. the embeddings for upstream gradient 1.  Parity unpinned (the package is absent); the
+ * definitions below are restated in float64 by tests/triplet_restate.py.  fp32, no float atomics: the same inputs give the same bits.
+ *   D [B, B]: distance 0 (Euclidean): d2 = |e_i|^2 - 2 e_i.e_j + |e_j|^2, D = 0 where d2 <= 0 or i == j (no gradient there), else
+ *     sqrt(d2); distance 1: D = 1 - e_i.e_j, the diagonal included (the cosine distance of the package when the caller has
+ *     L2-normalised the rows: carel_l2_normalize_fwd / _bwd).  D[i][j] and D[j][i] hold the same bits.
+ *   pos(a, j): labels equal and j != a; neg(a, j): labels differ.  Among exactly equal distances the lowest index is selected.
+ *   mode 0 semi-hard: per (a, p) the negative distance is the smallest D[a][n] > D[a][p], else the largest D[a][n], else 0 (no
+ *     negative: no gradient); loss = sum max(D[a][p] - Dneg + margin, 0) / #positive pairs (0 when there is none).
+ *   mode 1 all: l = D[a][p] - D[a][n] + margin over every valid (a, p, n); loss = sum max(l, 0) / (P + 1e-16), P = #{max(l, 0) > 1e-16}.
+ *   mode 2 hard: hp = max_j (pos ? D[a][j] : 0), hn = min_j (D[a][j] + (neg ? 0 : max_k D[a][k])); loss = mean_a max(hp - hn + margin, 0).
+ *   mode 3 hard soft-margin: the same hp, hn; loss = mean_a log1p(exp(hp - hn)) computed as a stable softplus; margin is ignored.
+ *   stats_out (optional): {positive pairs, valid triplets, active terms}: active = hinge terms > 0 (mode 0: pairs, mode 2: anchors),
+ *     P (mode 1), batch (mode 3).
+ *   work: f32 [carel_triplet_workspace_floats(batch)], owned by the caller, fully rewritten by every call.  Afterwards
+ *     work[0 .. B*B) holds D and work[B*B .. 2*B*B) holds W = d (sum of the loss terms) / d D (integer counts in the hinge modes).
+ * Four launches (three without demb) on `stream`; no allocation, no host synchronisation.  Errors before any launch: a NULL
+ * struct / emb / labels / loss_out / work, mode outside 0..3, distance outside 0..1 -> CAREL_ERR_ARG; batch outside 1..512 or
+ * hidden < 1 -> CAREL_ERR_SHAPE.  carel_triplet_workspace_floats is a pure host function (0 for a batch outside 1..512).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct carel_triplet_args {
+  const void* emb;      /* f32 [batch, hidden], contiguous */
+  const void* labels;   /* int32 [batch] */
+  int32_t batch, hidden;
+  int32_t mode;         /* 0 semi-hard, 1 all, 2 hard, 3 hard soft-margin */
+  int32_t distance;     /* 0 Euclidean, 1 one minus dot product */
+  float margin;
+  void* loss_out;       /* f32 [1] */
+  void* demb;           /* f32 [batch, hidden] or NULL */
+  void* stats_out;      /* int32 [3] or NULL */
+  void* work;           /* f32 [carel_triplet_workspace_floats(batch)] */
+} carel_triplet_args;
+int64_t carel_triplet_workspace_floats(int32_t batch);
+int carel_triplet_loss(const carel_triplet_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * RBF-MMD statistic.  Replaces MMDStatistic.__call__ (ref :547-569) + pdist (ref :580-589) and
  * their autograd backward.  mmd = 2*a01*sum(K12) + a00*(sum(K11)-tr K11) + a11*(sum(K22)-tr K22),
  * K = sum_alpha exp(-alpha * (eps + |d2|)), a00 = 1/(n1(n1-1)), a11 = 1/(n2(n2-1)), a01 = -1/(n1 n2).
