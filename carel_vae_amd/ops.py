@@ -98,8 +98,10 @@ def pdist_backward(s1, s2, grad, eps=1e-5):
 def _mmd_args(s1, s2, alphas, eps):
     if s1.dtype != torch.float32 or s2.dtype != torch.float32:
         raise L.CarelError("rbf_mmd: float32 samples required")
-    if s1.stride(1) != 1 or s2.stride(1) != 1:
-        raise L.CarelError("rbf_mmd: samples must be contiguous along the feature dimension")
+    if s1.stride(1) != 1 or s2.stride(1) != 1 or s1.shape[1] != s2.shape[1]:
+        raise L.CarelError("rbf_mmd: samples must share the feature width and be contiguous along it")
+    if len(alphas) > 8:
+        raise L.CarelError("rbf_mmd: at most 8 alphas (got %d)" % len(alphas))
     a = L.MmdArgs()
     a.s1, a.s2, a.ld1, a.ld2 = s1.data_ptr(), s2.data_ptr(), s1.stride(0), s2.stride(0)
     a.n1, a.n2, a.d, a.n_alphas, a.eps = s1.shape[0], s2.shape[0], s1.shape[1], len(alphas), eps
