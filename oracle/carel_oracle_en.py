@@ -115,7 +115,8 @@ def tail_forward(P, pooled, emo_labels, cau_labels, pair_labels, bow, iteration:
                  global_n: Optional[int] = None) -> Dict[str, torch.Tensor]:
     """Everything after pooler_output (:220-334).  eps: {"con": [con_dim], "e": [ec_dim], "c": [ec_dim]} -- sample_prior
     is called for content, emotion, cause in that order (:238-240), one vector per call shared by the batch (:417-423).
-    Labels are float [B, 1] (the `_en` dataset yields float emotion labels, :132)."""
+    Labels are float [B, 1] (the `_en` dataset yields float emotion labels, :132); they take the dtype of `pooled`, so a float64 run
+    smooths them in float64."""
     B = pooled.shape[0]
     D, Cd, V, ls = opt.ec_dim, opt.con_dim, opt.pair_bow_dim, opt.label_smoothing
 
@@ -134,9 +135,9 @@ def tail_forward(P, pooled, emo_labels, cau_labels, pair_labels, bow, iteration:
     def drop(t, site):
         m = O.dropout_scale_mask(seed, site, tuple(t.shape), pd, row_offset)
         return t if m is None else t * m
-    emo_y = emo_labels.view(B, -1).to(torch.float32)
-    cau_y = cau_labels.view(B, -1).to(torch.float32)
-    pair_y = pair_labels.view(B, -1).to(torch.float32)
+    emo_y = emo_labels.view(B, -1).to(pooled.dtype)
+    cau_y = cau_labels.view(B, -1).to(pooled.dtype)
+    pair_y = pair_labels.view(B, -1).to(pooled.dtype)
     bow_t = bow * (1 - ls) + ls / V                      # :447, :455, :548
     ec_t = lambda y: y * (1 - ls) + ls / opt.ec_num_class     # noqa: E731   :526, :565, :581
 

@@ -32,8 +32,9 @@ def split_lat(lat, opt):
 
 def tail_from_latents(P, lat: Dict[str, torch.Tensor], emo_labels, cau_labels, pair_labels, bow, kl_w_ec: float, kl_w_con: float, opt,
                       eps: Dict[str, torch.Tensor], weighting: str = "bow", train: bool = False, seed: Optional[int] = None,
-                      row_offset: int = 0) -> Dict[str, torch.Tensor]:
-    """Everything after the six latent heads.  lat: {mu_con, lv_con, mu_e, lv_e, mu_c, lv_c}; eps: {con, e, c}."""
+                      row_offset: int = 0, pos_weight=None) -> Dict[str, torch.Tensor]:
+    """Everything after the six latent heads.  lat: {mu_con, lv_con, mu_e, lv_e, mu_c, lv_c}; eps: {con, e, c}.
+    pos_weight: the pair term's pos_weight given explicitly (a data-parallel shard uses the global batch's); None: (B - sum y) / sum y."""
     assert weighting in ("plain", "bow")
     dt = lat["mu_e"].dtype
     B = lat["mu_e"].shape[0]
@@ -79,7 +80,7 @@ def tail_from_latents(P, lat: Dict[str, torch.Tensor], emo_labels, cau_labels, p
     cau_mul = O.bce_prob(torch.sigmoid(lin(drop(z_c, OE.SITE_CAUMUL), "cause_classifier")), ec_t(cau_y)).mean()
     xp = lin(drop(pair_emb, OE.SITE_PAIR), "pair_classifier")
     sy = pair_y.sum()
-    pair = O.bce_logits_posw(xp, ec_t(pair_y), (B - sy) / sy).mean()
+    pair = O.bce_logits_posw(xp, ec_t(pair_y), (B - sy) / sy if pos_weight is None else pos_weight).mean()
 
     def kl(mu, lv):
         return (-0.5 * (1 + lv - lv.exp() - mu.pow(2)).sum(dim=1)).mean()

@@ -9,16 +9,15 @@ measured shape by shape, the ratio weighted / unweighted is 0.65-1.4 for the vec
 numbers per image) and anything from 0.03 to 40 for a scalar term, which lands within 1e-9 of float64 by chance.  So "the error
 of a quantity" is its worst figure over the sweep, for both columns alike (measured: DESIGN.md section 7).
 """
-import ctypes as C
 from types import SimpleNamespace
 
 import pytest
 import torch
 
-from carel_vae_amd import _lib as L
 from oracle import carel_oracle as O
 from oracle import carel_oracle_en as OE
 from tests import en_bow_restate as R
+from tests.en_tail_restate import run_kernel          # the ctypes driver, shared with tests/test_gpu_en_tail_sweep.py
 
 pytestmark = pytest.mark.gpu
 
@@ -26,26 +25,11 @@ D = 24
 HEADS = dict(content_disc=lambda V, Cd: (V, D), content_classifier=lambda V, Cd: (V, Cd), decoder=lambda V, Cd: (V, 2 * D + Cd),
              emotion_disc=lambda V, Cd: (1, Cd), cause_disc=lambda V, Cd: (1, Cd), ec_disc=lambda V, Cd: (1, D), ce_disc=lambda V, Cd: (1, D),
              emotion_classifier=lambda V, Cd: (1, D), cause_classifier=lambda V, Cd: (1, D), pair_classifier=lambda V, Cd: (1, 2 * D))
-SMALL = ("emotion_disc", "cause_disc", "ec_disc", "ce_disc")
 IMAGES = ["g_cdisc_w0", "g_cdisc_b0", "g_cdisc_w1", "g_cdisc_b1", "g_cdisc_w2", "g_cdisc_b2", "d_ccls_w", "d_ccls_b", "dlat"]
 # what neither entry point weights: every term but the three content losses and the total, and every image below
 UNWEIGHTED_TERMS = [2, 3, 4, 5] + list(range(7, 15)) + list(range(16, 21))
 UNWEIGHTED_IMAGES = ["g_cdisc_w2", "g_cdisc_b2", "d_dec_w", "d_dec_b", "d_emo_w", "d_cau_w", "d_pair_w", "d_pair_b"] + \
     ["g_sdisc_w%d" % i for i in range(4)] + ["g_sdisc_ent_w%d" % i for i in range(4)] + ["g_sdisc_b%d" % i for i in range(4)]
-
-
-def al(n):
-    return (n + 63) & ~63
-
-
-def work_offsets(B, Cd, V):
-    """Where carel_en_tail_losses leaves the row statistics [4][B][2] and d vae / d lat [B, 2*Cd + 4*D] inside `work` (the carving order
-    of csrc/en_tail.hip: ten dropped-out copies, two [B, V] images, rowstat, three input-gradient blocks, the split-K slabs, dlat)."""
-    ZW = 2 * D + Cd
-    o = sum(al(B * k) for k in (D, D, Cd, Cd, D, D, Cd, D, D, 2 * D)) + 2 * al(B * V)
-    rowstat = o
-    o += al(8 * B) + al(B * Cd) + al(B * ZW) + al(B * 2 * D) + al(min(64, (V + 255) // 256) * B * ZW)
-    return rowstat, o
 
 
 def make_case(B, V, Cd, seed, drop_p=0.0, edit=None):
@@ -68,69 +52,6 @@ def make_case(B, V, Cd, seed, drop_p=0.0, edit=None):
     if edit is not None:
         edit(c)
     return c
-
-
-def run_kernel(c, weighted):
-    """One call of carel_en_tail_losses / carel_en_tail_losses_bow; returns terms and every image as CPU tensors."""
-    lib, dev = L.load(), "cuda"
-    B, V, Cd = c.B, c.V, c.Cd
-    ZW, LW = 2 * D + Cd, 2 * Cd + 4 * D
-    keep = {k: v.to(dev).contiguous() for k, v in c.P.items()}
-    inp = {k: getattr(c, k).to(dev).contiguous() for k in ("lat", "eps", "bow", "emo", "cau", "pair")}
-    dummy = torch.zeros(64, device=dev)
-    a = L.EnTailArgs()
-    a.batch, a.seq_len, a.hidden, a.ec_dim, a.con_dim, a.bow_dim = B, 1, 768, D, Cd, V
-    a.x_last_f32 = a.pooler_w = a.pooler_b = a.pooled = dummy.data_ptr()         # read by the latents / backward entry points only
-    for i in range(6):
-        a.head_w[i] = a.head_b[i] = dummy.data_ptr()
-    w = lambda k: keep[k].data_ptr()      # noqa: E731
-    a.cdisc_w, a.cdisc_b, a.ccls_w, a.ccls_b = w("content_disc.weight"), w("content_disc.bias"), w("content_classifier.weight"), w("content_classifier.bias")
-    for i, h in enumerate(SMALL):
-        a.sdisc_w[i], a.sdisc_b[i] = w(h + ".weight"), w(h + ".bias")
-    a.emo_w, a.emo_b, a.cau_w, a.cau_b = w("emotion_classifier.weight"), w("emotion_classifier.bias"), w("cause_classifier.weight"), w("cause_classifier.bias")
-    a.pair_w, a.pair_b, a.dec_w, a.dec_b = w("pair_classifier.weight"), w("pair_classifier.bias"), w("decoder.weight"), w("decoder.bias")
-    a.emo_labels, a.cau_labels, a.pair_labels, a.bow, a.eps = (inp[k].data_ptr() for k in ("emo", "cau", "pair", "bow", "eps"))
-    o = c.opt
-    a.w_con_adv, a.w_ec_adv, a.w_ecce_adv = o.con_adv_loss_weight, o.ec_adv_loss_weight, o.ecce_adv_loss_weight
-    a.w_ec_mul, a.w_con_mul, a.w_pair = o.ec_mul_loss_weight, o.con_mul_loss_weight, o.pair_mul_loss_weight
-    a.kl_w_ec, a.kl_w_con = c.kl
-    a.label_smoothing, a.epsilon, a.drop_p, a.drop_seed, a.drop_row_offset = o.label_smoothing, o.epsilon, c.drop_p, c.seed, 0
-    a.lat = inp["lat"].data_ptr()
-    out = dict(z=torch.full((B, ZW), float("nan"), device=dev), terms=torch.zeros(32, device=dev),
-               work=torch.full((lib.carel_en_tail_workspace_floats(B, D, Cd, V),), float("nan"), device=dev))
-    a.z, a.terms, a.work = out["z"].data_ptr(), out["terms"].data_ptr(), out["work"].data_ptr()
-
-    def img(name, shape):
-        out[name] = torch.full(shape, float("nan"), device=dev)
-        return out[name].data_ptr()
-    for i in range(3):
-        a.g_cdisc_w[i], a.g_cdisc_b[i] = img("g_cdisc_w%d" % i, (V, D)), img("g_cdisc_b%d" % i, (V,))
-    for i, h in enumerate(SMALL):
-        k = keep[h + ".weight"].shape
-        a.g_sdisc_w[i], a.g_sdisc_b[i] = img("g_sdisc_w%d" % i, k), img("g_sdisc_b%d" % i, (1,))
-        a.g_sdisc_ent_w[i], a.g_sdisc_ent_b[i] = img("g_sdisc_ent_w%d" % i, k), img("g_sdisc_ent_b%d" % i, (1,))
-    a.d_ccls_w, a.d_ccls_b = img("d_ccls_w", (V, Cd)), img("d_ccls_b", (V,))
-    a.d_emo_w, a.d_emo_b, a.d_cau_w, a.d_cau_b = img("d_emo_w", (1, D)), img("d_emo_b", (1,)), img("d_cau_w", (1, D)), img("d_cau_b", (1,))
-    a.d_pair_w, a.d_pair_b = img("d_pair_w", (1, 2 * D)), img("d_pair_b", (1,))
-    a.d_dec_w, a.d_dec_b = img("d_dec_w", (V, ZW)), img("d_dec_b", (V,))
-    st = L.current_stream()
-    if weighted:
-        bw = L.EnBowArgs()
-        out["bow_work"] = torch.full((lib.carel_en_tail_bow_workspace_floats(B, Cd, V),), float("nan"), device=dev)
-        bw.work = out["bow_work"].data_ptr()
-        L.check(lib.carel_en_tail_losses_bow(C.byref(a), C.byref(bw), st), "carel_en_tail_losses_bow")
-    else:
-        L.check(lib.carel_en_tail_losses(C.byref(a), st), "carel_en_tail_losses")
-    torch.cuda.synchronize()
-    r_off, d_off = work_offsets(B, Cd, V)
-    out["rowstat"] = out["work"][r_off:r_off + 8 * B].reshape(4, B, 2)[:3, :, 0].clone()       # the three content heads' sum_j omega bce
-    out["dlat"] = out["work"][d_off:d_off + B * LW].reshape(B, LW).clone()
-    if weighted:
-        out["xw"] = out["bow_work"][:B * Cd].reshape(B, Cd).clone()
-        out["con_w"] = out["bow_work"][al(B * Cd):al(B * Cd) + B * V].reshape(B, V).clone()
-        del out["bow_work"]
-    del out["work"]
-    return {k: v.cpu() for k, v in out.items()}
 
 
 def reference(c, weighting):
