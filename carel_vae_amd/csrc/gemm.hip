@@ -526,8 +526,10 @@ static GemmPlan gemm_plan(const GemmParams& p, int form, int epi, int splits, in
 #ifdef CAREL_GEMM_ABLATE
       if (npn == 2 && v >= 61 && v <= 68) return {PLAN_PP, 1, npn, v - 60};
 #endif
-      // (the same floor as gemm_pp_wgrad_splits: whatever carel_gemm_wgrad_splits proposes for this kernel must be taken by it)
-      if (npn && (v == 3 || wgs >= 64)) return {PLAN_PP, 1, npn, 0};
+      // (the same floor as gemm_pp_wgrad_splits: whatever carel_gemm_wgrad_splits proposes for this kernel must be taken by it;
+      // a shape only this kernel takes -- (256,96)-multiples that are neither (128,128)- nor (256,192)-multiples -- runs on it below
+      // the floor as well, as in the row-major-A branch: gemm_shape_ok accepted it on this kernel's account)
+      if (npn && (v == 3 || wgs >= 64 || !(v1_ok || big_ok))) return {PLAN_PP, 1, npn, 0};
     }
     if (K % (64 * splits)) return {PLAN_NONE, 1, 0, 0};       // (the tiles below want equal slices)
   } else {
@@ -933,6 +935,9 @@ static int gemm_prepare(const carel_gemm_args* a, int split_tile_factor, Planned
     default: return set_error(CAREL_ERR_ARG, "carel_gemm_bf16: unknown epilogue %d", epi);
   }
 #undef NEED
+  // (the 8-column epilogues store / load 16 bytes of bf16 per lane: a row pitch of 8 k + 4 elements would misalign every other row)
+  if (epi != EPI_BIAS_DROP_RESID && epi != EPI_ADD_F32 && epi != EPI_SLAB_F32 && (a->ldc & 7))
+    return set_error(CAREL_ERR_ARG, "carel_gemm_bf16: bf16 outputs and aux need ldc a multiple of 8 (ldc=%ld)", (long)a->ldc);
   const auto fn = launch_instance(form, epi);
   if (!fn) return set_error(CAREL_ERR_ARG, "carel_gemm_bf16: unsupported form/epilogue combination (%d,%d)", form, epi);
   *out = PlannedGemm{p, splits, gemm_plan(p, form, epi, splits, a->K), fn};

@@ -77,9 +77,13 @@ const char* carel_last_error(void);
 typedef struct carel_gemm_args {
   const void* A;        /* bf16 */
   const void* B;        /* bf16 */
-  int64_t lda, ldb, ldc; /* leading dimensions in elements */
-  int32_t M, N, K;      /* NT / NN: N multiple of 96 (any M; 256 x 96n kernel) or (M,N) multiples of (128,128) / (256,192);
-                           TN: (M,N) multiples of (256,96) or (128,128); K multiple of 64 (of 64*splits for the 128x128 kernel) */
+  int64_t lda, ldb, ldc; /* leading dimensions in elements: lda / ldb multiples of 8; ldc a multiple of 4 for the f32-output epilogues,
+                            of 8 for every epilogue with a bf16 output or aux_bf16 (16-byte stores / loads per lane) */
+  int32_t M, N, K;      /* NT / NN: N multiple of 96 with K >= 256 (any M; 256 x 96n kernel) or (M,N) multiples of (128,128) / (256,192);
+                           TN: (M,N) multiples of (128,128) or (256,192) with K a multiple of 64*splits, or of (256,96) with K a
+                           multiple of 64 and at least 4 K tiles of 64 per slice (K / 64 / splits >= 4: the 256 x 96n kernel, which
+                           takes such a shape at any grid size and deals the K tiles to the slices as evenly as possible).
+                           K is a multiple of 64 in every form */
   int32_t form;         /* CAREL_GEMM_* */
   int32_t epilogue;     /* CAREL_EPI_*  */
   int32_t splits;       /* split-K factor (slab epilogue only), else 1 */

@@ -19,7 +19,7 @@ def to_bf16_bits(t: torch.Tensor) -> torch.Tensor:
 
 def gemm(A, B, form, epi, M, N, K, splits=1, out_bf16=None, out2_bf16=None, out_f32=None, bias=None,
          resid=None, aux=None, drop=(0, 0, 0, 0.0), lda=None, ldb=None, ldc=None, colsum_part=None, colsum_a=None, splitk_ws=None,
-         ws_zeroed=False, resid_ln=None):
+         ws_zeroed=False, resid_ln=None, drop_row_map=None):
     a = L.GemmArgs()
     a.A, a.B = A.data_ptr(), B.data_ptr()
     a.lda = lda if lda is not None else A.stride(0)
@@ -31,6 +31,7 @@ def gemm(A, B, form, epi, M, N, K, splits=1, out_bf16=None, out2_bf16=None, out_
                     ("resid_f32", resid), ("aux_bf16", aux)):
         setattr(a, name, None if t is None else t.data_ptr())
     a.drop_seed, a.drop_site, a.drop_idx_offset, a.drop_p = drop
+    a.drop_row_map = None if drop_row_map is None else drop_row_map.data_ptr()          # int32 [M]
     a.colsum_part = None if colsum_part is None else colsum_part.data_ptr()
     a.colsum_a = None if colsum_a is None else colsum_a.data_ptr()
     a.splitk_ws = None if splitk_ws is None else splitk_ws.data_ptr()

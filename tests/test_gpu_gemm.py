@@ -212,10 +212,12 @@ def test_internal_split_k_with_workspace_matches_single_pass():
     for use_ws in (None, ws):
         out = torch.empty((M, N), device="cuda")
         gemm(A, W, L.GEMM_NT, L.EPI_BIAS_DROP_RESID, M, N, K, out_f32=out, bias=b, resid=r, drop=(7, 5, 0, 0.1), splitk_ws=use_ws,
-             **({"lda": K, "ldb": K}))
+             drop_row_map=rowmap, **({"lda": K, "ldb": K}))
         outs.append(out)
     assert rel_err(outs[1], outs[0]) < 1e-6
-    assert rel_err(outs[1], A.double() @ W.double().t() + b.double() + r.double()) < 0.4     # dropout on: loose sanity only
+    idx = (rowmap.cpu().numpy().astype(np.uint64)[:, None] * np.uint64(N) + np.arange(N, dtype=np.uint64)[None, :]).astype(np.uint32)
+    keep = torch.from_numpy(O.dropout_keep(7, 5, idx, 0.1).astype(np.float64) / 0.9).cuda()        # element rowmap[row] * ldc + col
+    assert rel_err(outs[1], (A.double() @ W.double().t() + b.double()) * keep + r.double()) < TOL
     A2, W2 = _rand((M, 2304), 1, 35).bfloat16(), _rand((2304, N), 0.05, 36).bfloat16()
     o1, o2 = torch.empty((M, N), device="cuda"), torch.empty((M, N), device="cuda")
     gemm(A2, W2, L.GEMM_NN, L.EPI_ADD_F32, M, N, 2304, out_f32=o1, resid=r)
