@@ -94,6 +94,21 @@ __device__ void wave_normalise(int mode, const float* z, float* p, float* sh, fl
   if (v1) { const float d = fmaxf(x1 - tau, 0.f); p[lane + 64] = d * d; }
 }
 
+// Softmax backward of one row, two values per lane (p = 0, dp = 0 beyond S):  dz = p ((dp - c) - sum p (dp - c)),  c = dp at the largest p
+// (the lowest index on a tie).  For sum p = 1 that is p (dp - sum p dp); in float32 the p of a nearly one-hot row miss sum p = 1 by a
+// rounding, and the plain form loses the dominant token's dz -- a difference of nearly equal numbers -- to it.  With the shift the
+// dominant term of the sum is an exact zero and every other term is small.
+__device__ __forceinline__ void softmax_backward(float p0, float p1, float g0, float g1, int lane, float& r0, float& r1) {
+  const float pm = wave_max(fmaxf(p0, p1));
+  const float at = p0 == pm ? (float)lane : (p1 == pm ? (float)(lane + 64) : 128.f);
+  const int idx = (int)-wave_max(-at);
+  const float ca = __shfl(g0, idx & 63, 64), cb = __shfl(g1, idx & 63, 64);
+  const float c = idx < 64 ? ca : cb;
+  const float h0 = g0 - c, h1 = g1 - c;
+  const float sp = wave_sum(p0 * h0 + p1 * h1);
+  r0 = p0 * (h0 - sp); r1 = p1 * (h1 - sp);
+}
+
 // out[k][b][s] = x[b*S + s] . vec_k(b),  k = a*G + g,  vec_k(b) = vec + a*v_as + b*v_bs + g*768.  Grid (S / 16, B).
 template <int NV>
 __global__ __launch_bounds__(256) void adapter_rowdot_kernel(const float* __restrict__ x, int S, int B, const float* __restrict__ vec,
@@ -230,8 +245,7 @@ __global__ __launch_bounds__(192) void adapter_dzdh_kernel(int S, int B, int G, 
     const float g0 = v0 ? dz[k][lane] : 0.f, g1 = v1 ? dz[k][lane + 64] : 0.f;
     float r0, r1;
     if (mode == 0) {
-      const float sp = wave_sum(p0 * g0 + p1 * g1);
-      r0 = p0 * (g0 - sp); r1 = p1 * (g1 - sp);
+      softmax_backward(p0, p1, g0, g1, lane, r0, r1);
     } else if (mode == 1) {
       const float n = wave_sum((p0 > 0.f ? 1.f : 0.f) + (p1 > 0.f ? 1.f : 0.f));
       const float mean = wave_sum((p0 > 0.f ? g0 : 0.f) + (p1 > 0.f ? g1 : 0.f)) / n;
@@ -359,8 +373,7 @@ __global__ __launch_bounds__(256) void adapter_wgrad_dz_kernel(int rows, int S, 
   const float g0 = v0 ? gr[lane] : 0.f, g1 = v1 ? gr[lane + 64] : 0.f;
   float r0, r1;
   if (mode == 0) {
-    const float sp = wave_sum(p0 * g0 + p1 * g1);
-    r0 = p0 * (g0 - sp); r1 = p1 * (g1 - sp);
+    softmax_backward(p0, p1, g0, g1, lane, r0, r1);
   } else if (mode == 1) {
     const float n = wave_sum((p0 > 0.f ? 1.f : 0.f) + (p1 > 0.f ? 1.f : 0.f));
     const float mean = wave_sum((p0 > 0.f ? g0 : 0.f) + (p1 > 0.f ? g1 : 0.f)) / n;
@@ -459,6 +472,13 @@ static int ad_check(const carel_adapter_args* a, const char* who) {
   if (a->batch < 1 || a->batch_padded < a->batch) return set_error(CAREL_ERR_SHAPE, "%s: need 1 <= batch <= batch_padded", who);
   if (a->seq_len < 32 || a->seq_len > 128 || a->seq_len % 32) return set_error(CAREL_ERR_SHAPE, "%s: seq_len must be 32, 64, 96 or 128", who);
   if (!a->u || !a->work) return set_error(CAREL_ERR_ARG, "%s: null u / work", who);
+  // the sample index is a grid y coordinate (rowdot, combine: batch; dzdh: batch_padded)
+  if (a->batch_padded > 65535) return set_error(CAREL_ERR_SHAPE, "%s: batch_padded must be <= 65535", who);
+  // every kernel moves these as float4 (NULL where a call does not use one: the entry points check that)
+  const void* vec[] = {a->u, a->work, a->x_f32, a->out_f32, a->d_out_f32, a->dx_f32, a->query[0], a->query[1], a->q_w[0], a->q_w[1],
+                       a->k_w[0], a->k_w[1], a->v_w[0], a->v_w[1], a->o_w[0], a->o_w[1]};
+  for (const void* q : vec)
+    if ((uintptr_t)q & 15) return set_error(CAREL_ERR_ARG, "%s: u, work, x, out, d_out, dx, query and the weights must be 16-byte aligned", who);
   return CAREL_OK;
 }
 

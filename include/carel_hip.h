@@ -560,7 +560,8 @@ int carel_pair_probs(const void* lat, const void* eps_e, const void* eps_c, cons
  *   u_h = W_k,h^T q_h / sqrt(d)  (carel_adapter_build_u),  scores_h[b,s] = H[b,s] . u_h
  * -- no [B*S, 768] x [768, 768] GEMM.  For raw mode the value projection and out_proj act after the weighted sum (sum_s p = 1).
  * Both adapters go through one pass over H.  f32 throughout; exact sort-based normalisers (ties included); no atomics (results
- * are bitwise repeatable).  seq_len in {32, 64, 96, 128}; G | 768, G <= 12; G = 1 for modes 1 / 2.
+ * are bitwise repeatable).  seq_len in {32, 64, 96, 128}; G | 768, G <= 12; G = 1 for modes 1 / 2; batch_padded <= 65535;
+ * u, work, x, out, d_out, dx, query and the weight matrices 16-byte aligned (anything else is refused before any launch).
  *
  * Weights per adapter a (0 = emotion, 1 = cause), each [768, 768] row-major (nn.Linear layout) / [768]:
  *   modes 1 / 2: q_w / q_b = q_proj, k_w = k_proj.weight;   v_* / o_* unused (may be NULL)
@@ -590,8 +591,8 @@ int carel_adapter_build_u(const carel_adapter_args* args, void* stream);
 /* out (and p in work) from x and u */
 int carel_adapter_forward(const carel_adapter_args* args, void* stream);
 /* dx from d_out, x, u and the p of the preceding forward:  dctx = d_out (modes 1 / 2) or W_v,h^T (W_o^T d_out)_h (raw);
- * dp[h,s] = H_s . dctx_h;  dz = normaliser backward (softmax p(dp - sum p dp); sparsemax dp - mean_support dp on p > 0;
- * entmax15 g dp - (sum g dp / sum g) g with g = sqrt(p));  dH_s = sum_adapters sum_h p[h,s] dctx_h + dz[h,s] u_h.
+ * dp[h,s] = H_s . dctx_h;  dz = normaliser backward (softmax p(dp - sum p dp), evaluated with dp shifted by its value at the
+ * largest p so that a one-hot row does not cancel; sparsemax dp - mean_support dp on p > 0; entmax15 g dp - (sum g dp / sum g) g with g = sqrt(p));  dH_s = sum_adapters sum_h p[h,s] dctx_h + dz[h,s] u_h.
  * Adapter weight gradients are not formed (the reference never applies them: its get_params() leaves the adapters out, :460). */
 int carel_adapter_backward(const carel_adapter_args* args, void* stream);
 

@@ -181,6 +181,17 @@ def _adapter_ref(model, Hs):
 @pytest.mark.parametrize("mode,heads", [("entmax", 4), ("sparsemax", 4), ("raw", 4)])
 @pytest.mark.parametrize("B,S", [(8, 128), (7, 96)])
 def test_wiring_on_the_models_own_last_hidden_states(mode, heads, B, S, monkeypatch):
+    _wiring(mode, heads, B, S, monkeypatch)
+
+
+@pytest.mark.parametrize("mode,heads", [("sparsemax", 4), ("raw", 6)])
+def test_wiring_at_length_64_and_a_head_count_of_six(mode, heads, monkeypatch):
+    """The model itself across S = 64 (the length at which no lane of wave_normalise owns a second position) and the NV = 12
+    instantiation of the raw kernels, which no other model-level test launches."""
+    _wiring(mode, heads, 5, 64, monkeypatch)
+
+
+def _wiring(mode, heads, B, S, monkeypatch):
     model = _model(mode, heads)
     b = _batch(B, S)
     Bp = model._padded_batch(B, S)
