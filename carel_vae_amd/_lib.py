@@ -298,6 +298,7 @@ SIGNATURES = {
     "carel_scale_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "carel_tail_pair_dead_offset": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "carel_pair_probs": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "carel_pair_probs_draws": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 3 + [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_void_p]),
     "carel_adapter_workspace_floats": (C.c_int64, [C.c_int32] * 3),
     "carel_adapter_build_u": (C.c_int, [C.POINTER(AdapterArgs), C.c_void_p]),
     "carel_adapter_forward": (C.c_int, [C.POINTER(AdapterArgs), C.c_void_p]),

@@ -448,6 +448,15 @@ __global__ __launch_bounds__(256) void sample_z_kernel(const float* __restrict__
   z[e] = sample_z(lat + (long)b * 4 * D, eps_e, eps_c, D, k);
 }
 
+// The pair head on one sampled pair of latents, stated once for pair_prob_kernel and pair_draws_kernel: component k of the emotion and of
+// the cause sample (mu + eps * e^lv, with ex = e^lv) enters the logit in this order, and the logit becomes a probability by pair_sigmoid.
+__device__ __forceinline__ float pair_logit_step(float s, float w_e, float mu_e, float eps_e, float ex_e, float w_c, float mu_c, float eps_c,
+                                                 float ex_c) {
+  s = fmaf(w_e, mu_e + eps_e * ex_e, s);
+  return fmaf(w_c, mu_c + eps_c * ex_c, s);
+}
+__device__ __forceinline__ float pair_sigmoid(float s) { return 1.0f / (1.0f + expf(-s)); }
+
 // eval-mode pair probabilities (get_pair_preds :265-282): sigmoid(w . [mu_e + eps_e e^lv_e, mu_c + eps_c e^lv_c] + b)
 __global__ __launch_bounds__(256) void pair_prob_kernel(const float* __restrict__ lat, const float* __restrict__ eps_e,
                                                         const float* __restrict__ eps_c, const float* __restrict__ w,
@@ -456,11 +465,87 @@ __global__ __launch_bounds__(256) void pair_prob_kernel(const float* __restrict_
   if (b >= B) return;
   const float* row = lat + (long)b * 4 * D;
   float s = bias[0];
-  for (int k = 0; k < D; ++k) {
-    s = fmaf(w[k], reparam(row[k], eps_e[k], row[D + k]), s);
-    s = fmaf(w[D + k], reparam(row[2 * D + k], eps_c[k], row[3 * D + k]), s);
+  for (int k = 0; k < D; ++k)
+    s = pair_logit_step(s, w[k], row[k], eps_e[k], expf(row[D + k]), w[D + k], row[2 * D + k], eps_c[k], expf(row[3 * D + k]));
+  prob[b] = pair_sigmoid(s);
+}
+
+// Many noise draws over the same latents (carel_pair_probs_draws): the encoder, pooler / adapters and latent heads are deterministic in
+// eval mode, so a re-evaluation with fresh noise (get_pair_preds, quirk Q6) only changes eps_e / eps_c.  A workgroup owns PD_ROWS rows
+// (one per thread: the row's mu and e^lv stay in registers) and blockIdx.y walks the draws in slices of PD_SLICE, whose noise and the
+// pair head's weights sit in LDS (every lane reads the same word: a broadcast).  Per (draw, row) the arithmetic is pair_prob_kernel's.
+// Counts (TP / FP / FN per draw and group, prediction = prob > 0.5) are integers end to end: a ballot of the predictions per wave and
+// draw, popcounts against the wave's label and group masks (formed once), one LDS slot per wave, then one integer global add per
+// (workgroup, draw, group, kind) into counts that the host entry has zeroed on the same stream.  Integer sums do not depend on order.
+constexpr int PD_ROWS = 256;
+constexpr int PD_SLICE = 32;
+constexpr int PD_MAXG = 8;
+
+template <int DP>      // ec_dim rounded up to a multiple of 8: the extent of the register arrays
+__global__ __launch_bounds__(PD_ROWS) void pair_draws_kernel(const float* __restrict__ lat, const float* __restrict__ eps_e,
+                                                             const float* __restrict__ eps_c, const float* __restrict__ w,
+                                                             const float* __restrict__ bias, int n, int D, int K, float* __restrict__ prob,
+                                                             const float* __restrict__ labels, const int* __restrict__ groups, int G,
+                                                             int* __restrict__ counts) {
+  __shared__ float s_ee[PD_SLICE * DP], s_ec[PD_SLICE * DP], s_w[2 * DP];
+  __shared__ int s_cnt[PD_ROWS / 64][PD_SLICE][3 * PD_MAXG];
+  const int t = threadIdx.x, b = blockIdx.x * PD_ROWS + t, k0 = blockIdx.y * PD_SLICE;
+  const int nd = K - k0 < PD_SLICE ? K - k0 : PD_SLICE;
+  for (int i = t; i < nd * D; i += PD_ROWS) {
+    const int d = i / D, k = i - d * D;
+    s_ee[d * DP + k] = eps_e[(long)(k0 + d) * D + k];
+    s_ec[d * DP + k] = eps_c[(long)(k0 + d) * D + k];
   }
-  prob[b] = 1.0f / (1.0f + expf(-s));
+  for (int i = t; i < 2 * D; i += PD_ROWS) s_w[i < D ? i : DP + (i - D)] = w[i];
+  const bool valid = b < n;
+  const float* row = lat + (long)(valid ? b : n - 1) * 4 * D;      // threads past the last row stay for the ballots; they write nothing
+  float mu_e[DP], ex_e[DP], mu_c[DP], ex_c[DP];
+#pragma unroll
+  for (int k = 0; k < DP; ++k) {
+    const bool in = k < D;
+    mu_e[k] = in ? row[k] : 0.0f;
+    ex_e[k] = in ? expf(row[D + k]) : 0.0f;
+    mu_c[k] = in ? row[2 * D + k] : 0.0f;
+    ex_c[k] = in ? expf(row[3 * D + k]) : 0.0f;
+  }
+  const float b0 = bias[0];
+  unsigned long long pm = 0, gm[PD_MAXG];
+  if (counts) {
+    pm = __ballot(valid && labels[b] == 1.0f);
+    const int grp = valid ? (groups ? groups[b] : 0) : -1;           // an id outside [0, G) is in no group
+#pragma unroll
+    for (int g = 0; g < PD_MAXG; ++g) gm[g] = __ballot(grp == g);
+  }
+  __syncthreads();
+  const int wave = t >> 6, lane = t & 63;
+  for (int d = 0; d < nd; ++d) {
+    float s = b0;
+#pragma unroll
+    for (int k = 0; k < DP; ++k)
+      if (k < D) s = pair_logit_step(s, s_w[k], mu_e[k], s_ee[d * DP + k], ex_e[k], s_w[DP + k], mu_c[k], s_ec[d * DP + k], ex_c[k]);
+    const float p = pair_sigmoid(s);
+    if (prob && valid) prob[(long)(k0 + d) * n + b] = p;
+    if (counts) {
+      const unsigned long long pr = __ballot(valid && p > 0.5f);      // .round() of a probability: exactly 0.5 predicts 0 (ref :282)
+      if (lane == 0) {
+#pragma unroll
+        for (int g = 0; g < PD_MAXG; ++g)
+          if (g < G) {
+            s_cnt[wave][d][3 * g + 0] = __popcll(pr & pm & gm[g]);
+            s_cnt[wave][d][3 * g + 1] = __popcll(pr & ~pm & gm[g]);
+            s_cnt[wave][d][3 * g + 2] = __popcll(~pr & pm & gm[g]);
+          }
+      }
+    }
+  }
+  if (!counts) return;
+  __syncthreads();
+  for (int i = t; i < nd * 3 * G; i += PD_ROWS) {
+    const int d = i / (3 * G), j = i - d * 3 * G;
+    int c = 0;
+    for (int wv = 0; wv < PD_ROWS / 64; ++wv) c += s_cnt[wv][d][j];
+    if (c) atomicAdd(&counts[(long)(k0 + d) * 3 * G + j], c);
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -787,6 +872,36 @@ extern "C" int carel_pair_probs(const void* lat, const void* eps_e, const void* 
   hipLaunchKernelGGL(pair_prob_kernel, dim3((batch + 255) / 256), dim3(256), 0, stream, (const float*)lat, (const float*)eps_e,
                      (const float*)eps_c, (const float*)pair_w, (const float*)pair_b, batch, ec_dim, (float*)prob);
   return check_launch("pair_prob_kernel");
+}
+
+extern "C" int carel_pair_probs_draws(const void* lat, const void* eps_e, const void* eps_c, const void* pair_w, const void* pair_b,
+                                      int32_t n, int32_t ec_dim, int32_t n_draws, void* prob, const void* labels, const void* groups,
+                                      int32_t n_groups, void* counts, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const char* who = "carel_pair_probs_draws";
+  if (!lat || !eps_e || !eps_c || !pair_w || !pair_b) return set_error(CAREL_ERR_ARG, "%s: null tensor", who);
+  if (!prob && !counts) return set_error(CAREL_ERR_ARG, "%s: neither prob nor counts to write", who);
+  if (counts && !labels) return set_error(CAREL_ERR_ARG, "%s: counts need labels", who);
+  if (n < 1 || n_draws < 1) return set_error(CAREL_ERR_SHAPE, "%s: n and n_draws must be >= 1", who);
+  if (ec_dim < 1 || ec_dim > 32) return set_error(CAREL_ERR_SHAPE, "%s: ec_dim must be in 1..32", who);
+  if (n_groups < 1 || n_groups > PD_MAXG) return set_error(CAREL_ERR_SHAPE, "%s: n_groups must be in 1..%d", who, PD_MAXG);
+  const long slices = ((long)n_draws + PD_SLICE - 1) / PD_SLICE;
+  if (slices > 65535) return set_error(CAREL_ERR_SHAPE, "%s: at most %d draws per call", who, 65535 * PD_SLICE);
+  if (counts) {
+    hipError_t e = hipMemsetAsync(counts, 0, (size_t)n_draws * n_groups * 3 * sizeof(int), stream);
+    if (e != hipSuccess) return set_error(CAREL_ERR_HIP, "%s: memset: %s", who, hipGetErrorString(e));
+  }
+  const dim3 grid((n + PD_ROWS - 1) / PD_ROWS, (unsigned)slices);
+#define CAREL_PD_LAUNCH(DP)                                                                                                             \
+  hipLaunchKernelGGL(pair_draws_kernel<DP>, grid, dim3(PD_ROWS), 0, stream, (const float*)lat, (const float*)eps_e, (const float*)eps_c, \
+                     (const float*)pair_w, (const float*)pair_b, n, ec_dim, n_draws, (float*)prob, (const float*)labels,                  \
+                     (const int*)groups, n_groups, (int*)counts)
+  if (ec_dim <= 8) CAREL_PD_LAUNCH(8);
+  else if (ec_dim <= 16) CAREL_PD_LAUNCH(16);
+  else if (ec_dim <= 24) CAREL_PD_LAUNCH(24);
+  else CAREL_PD_LAUNCH(32);
+#undef CAREL_PD_LAUNCH
+  return check_launch("pair_draws_kernel");
 }
 
 // ---- the two LDS plans of carel_tail_losses (its batch limit), shared with carel_tail_batch_limit

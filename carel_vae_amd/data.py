@@ -95,10 +95,14 @@ def _parse_pairs(line, language):
     return [(e, c) for e, c in pairs]
 
 
-def read_ECPE_data(file_path, test=False, language="zh", rng=random):
+def read_ECPE_data(file_path, test=False, language="zh", rng=random, newsplit=False, bow_optimize=False):
     """Returns (df[pair,label,emotion], docs_pair_size, num_unpred_emotions) exactly like the reference:
     same row order, same use of `random.sample` for the training negatives (so `random.seed(42)`, :27,
-    reproduces the reference's rows), same treatment of predicted emotions in test files."""
+    reproduces the reference's rows), same treatment of predicted emotions in test files.
+    newsplit=True: the reader of drl_classifier_ec_mmd_final_mul_newsplit_emnlp.py (:833-958) -- a fourth column `temporal_order`
+    (bool: the cause clause is not after the emotion clause, cau_sen_id <= emo_sen_id, :933 / :952) and, for language "en" with
+    bow_optimize (bool or the script's "true" / "false"), clauses that keep their spaces, joined with " [SEP] " (:926-928)."""
+    keep_spaces = bool(newsplit) and language == "en" and bow_optimize in (True, "true")
     rows, docs_pair_size, num_unpred = [], [], 0
     with open(file_path, encoding="utf8") as f:
         while True:
@@ -145,16 +149,36 @@ def read_ECPE_data(file_path, test=False, language="zh", rng=random):
                         neg_pairs.append((e, c))
 
             def text(i):
-                return sentence_list[i - 1].strip().split(",")[3].replace(" ", "")
-            for e, c in pos_pairs:
-                rows.append((text(e) + "[SEP]" + text(c), 1, sen_emo[e]))
-            for e, c in neg_pairs:
-                rows.append((text(e) + "[SEP]" + text(c), 0, sen_emo[e]))
+                t = sentence_list[i - 1].strip().split(",")[3]
+                return t if keep_spaces else t.replace(" ", "")
+            sep = " [SEP] " if keep_spaces else "[SEP]"
+            for label, pairs in ((1, pos_pairs), (0, neg_pairs)):
+                for e, c in pairs:
+                    row = (text(e) + sep + text(c), label, sen_emo[e])
+                    rows.append(row + (c <= e,) if newsplit else row)
             docs_pair_size.append(len(pos_pairs) + len(neg_pairs))
-    df = pd.DataFrame(rows, columns=["pair", "label", "emotion"])
+    columns = ["pair", "label", "emotion"] + (["temporal_order"] if newsplit else [])
+    df = pd.DataFrame(rows, columns=columns)
     if len(df) == 0:
-        df = pd.DataFrame(columns=["pair", "label", "emotion"])
+        df = pd.DataFrame(columns=columns)
+    if newsplit:
+        df["temporal_order"] = df["temporal_order"].astype(bool)
     return df, docs_pair_size, num_unpred
+
+
+def newsplit_paths(opt):
+    """(train_path, test_path) as the body of drl_classifier_ec_mmd_final_mul_newsplit_emnlp.py selects them (:1204-1226): the test file
+    depends on the language, on `predicted_emotion` and, for English without predicted emotions, on `bow_optimize`."""
+    root = "data/ECPE_new_dataset/" if opt.language == "zh" else "domains/Englishnovel_multiple/"
+    train_path = root + opt.source_domain + ".txt"
+    predicted = "pair_data/predicted_emotion/source_{}/".format(opt.source_domain) + opt.target_domain + ".txt"
+    if opt.language == "zh":
+        test_path = predicted if opt.predicted_emotion == "true" else "data/ECPE_new_dataset/" + opt.target_domain + "_test.txt"
+    elif opt.predicted_emotion == "false":
+        test_path = "pair_data/emotion/" + opt.target_domain + ("_optimize.txt" if opt.bow_optimize == "true" else ".txt")
+    else:
+        test_path = predicted
+    return train_path, test_path
 
 
 # ----------------------------------------------------------------------------------------------
@@ -171,8 +195,12 @@ class ECPEDataset(torch.utils.data.Dataset):
     vocabulary lookup is a dict instead of the reference's O(V) list.index per word -- same outputs.
     """
 
-    def __init__(self, df, tokenizer=None, bow=None, max_len=128, segmenter=None, pretokenize=True):
+    _bow_words = False          # (subclasses that fill the caches themselves never set it)
+
+    def __init__(self, df, tokenizer=None, bow=None, max_len=128, segmenter=None, pretokenize=True, language="zh", bow_optimize=False):
         self.tokenizer = tokenizer
+        # the newsplit script (:132-140): English with the optimised vocabulary counts bow_tokenize's words; everything else keeps the CJK filter
+        self._bow_words = language == "en" and bow_optimize in (True, "true")
         self.pairs = df["pair"].reset_index(drop=True)
         self.labels = df["label"].values
         self.emo_labels = df["emotion"].values
@@ -195,13 +223,15 @@ class ECPEDataset(torch.utils.data.Dataset):
     def _get_bow_representations(self, text_pair):
         """(:100-119) non-CJK characters are stripped even for English input."""
         rep = np.zeros(shape=len(self.bow_features), dtype=np.float32)
-        text = _NON_ZH.sub(r"", str(text_pair))
-        if text:
-            seg = self._segmenter or _default_segmenter()
-            for word in seg(text):
-                j = self._bow_index.get(word)
-                if j is not None:
-                    rep[j] += 1
+        if self._bow_words:
+            words = bow_tokenize(str(text_pair), self.tokenizer)
+        else:
+            text = _NON_ZH.sub(r"", str(text_pair))
+            words = (self._segmenter or _default_segmenter())(text) if text else []
+        for word in words:
+            j = self._bow_index.get(word)
+            if j is not None:
+                rep[j] += 1
         rep /= np.max([np.sum(rep), 1])
         return rep
 

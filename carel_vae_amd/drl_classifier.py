@@ -51,6 +51,21 @@ def make_gan_opt(**kw):
     return SimpleNamespace(**d)
 
 
+# drl_classifier_ec_mmd_final_mul_newsplit_emnlp.py:30-75: the parser defaults of the new-split driver (the EMNLP model; the flags stay
+# the script's strings).  `confounding` is only printed by the script.
+NEWSPLIT_OPT = dict(DEFAULT_OPT, bow_optimize="true", source_domain="home", target_domain="education", bow_file="data/all_data_pair_zh.txt",
+                    self_strategy="temporal_order_modification", adapter="false", head_number=4, confounding="false",
+                    predicted_emotion="true", round_up="true")
+
+
+def make_newsplit_opt(**kw):
+    """The argparse namespace of drl_classifier_ec_mmd_final_mul_newsplit_emnlp.py (:30-75) with its defaults (plus pair_bow_dim and
+    model_id, which the script computes)."""
+    d = dict(NEWSPLIT_OPT)
+    d.update(kw)
+    return SimpleNamespace(**d)
+
+
 REL_KEY = "encoder.encoder.relative_attention_bias.weight"
 
 
@@ -1281,10 +1296,20 @@ class DrlClassifier(nn.Module):
         128 / 256 / 512 / 1 024 -- larger GEMM grids and fewer length read-backs."""
         self._require_cuda()
         ops._chk_cuda(input_ids, att_masks, token_type_ids)
+        eps_e, eps_c = self._draw_noise(input_ids.device)
+        lat = self.pair_latents(input_ids, att_masks, token_type_ids, chunk=chunk)
+        W, _ = self._tail_weights()
+        return ops.pair_probs(lat, eps_e, eps_c, W["pair_classifier.weight"], W["pair_classifier.bias"], self.opt.ec_dim)
+
+    def pair_latents(self, input_ids, att_masks, token_type_ids, chunk=1024):
+        """The deterministic front of `pair_probabilities` (extension): eval-mode encoder in chunks, [CLS]-only last layer, pooler or
+        adapters, latent heads -> lat [N, 4 * ec_dim] f32 = [mu_e | log_var_e | mu_c | log_var_c] on the device.  No noise is drawn.
+        `pair_probabilities_from` / `draw_counts` then evaluate any number of noise draws on it without another encoder pass."""
+        self._require_cuda()
+        ops._chk_cuda(input_ids, att_masks, token_type_ids)
         dev = input_ids.device
-        eps_e, eps_c = self._draw_noise(dev)
         N, S0 = input_ids.shape
-        out = torch.empty(N, device=dev, dtype=torch.float32)
+        out = torch.empty((N, 4 * self.opt.ec_dim), device=dev, dtype=torch.float32)
         self._refresh_shadow()
         lib = L.load()
         for s in range(0, N, chunk):
@@ -1314,13 +1339,67 @@ class DrlClassifier(nn.Module):
                                cls_rows=cls.compact if cls is not None else (None if pack is None else pack.cu), head_in=head_in)
             ta._keep = (pack, cls)
             ops.tail_latents(ta)
-            out[s:s + B] = ops.pair_probs(buf.lat, eps_e, eps_c, W["pair_classifier.weight"], W["pair_classifier.bias"], self.opt.ec_dim)
+            out[s:s + B] = buf.lat
         return out
 
-    def get_pair_preds(self, input_ids, att_masks, token_type_ids):
-        """Reference `get_pair_preds` (:265-282): nested python list [[0.|1.], ...]."""
-        prob = self.pair_probabilities(input_ids, att_masks, token_type_ids)
-        return prob.reshape(-1, 1).cpu().detach().numpy().round().tolist()
+    def _draws_noise(self, dev, n_draws, noise):
+        D = self.opt.ec_dim
+        if noise is None:            # what n_draws successive forward / pair_probabilities calls draw: emotion then cause, per draw
+            if int(n_draws) < 1:
+                raise L.CarelError("n_draws must be >= 1")
+            pairs = [self._draw_noise(dev) for _ in range(int(n_draws))]
+            return torch.stack([p[0] for p in pairs]), torch.stack([p[1] for p in pairs])
+        eps_e, eps_c = (torch.as_tensor(x).to(dev, torch.float32).reshape(-1, D).contiguous() for x in noise)
+        if eps_e.shape != eps_c.shape or eps_e.shape[0] < 1:
+            raise L.CarelError("noise must be (eps_e [K, ec_dim], eps_c [K, ec_dim]) with K >= 1")
+        return eps_e, eps_c
+
+    def pair_probabilities_from(self, lat, n_draws=1, noise=None, return_noise=False):
+        """prob [K, N] f32: `pair_probabilities` for K noise draws on the latents of `pair_latents`, in one launch (extension).  Without
+        `noise` it draws what K successive `pair_probabilities` calls draw, so row k has the bits of the k-th such call from the same
+        generator state; noise = (eps_e [K, D], eps_c [K, D]) replays chosen draws (return_noise=True hands them back)."""
+        self._require_cuda()
+        eps_e, eps_c = self._draws_noise(lat.device, n_draws, noise)
+        W, _ = self._tail_weights()
+        prob, _ = ops.pair_probs_draws(lat, eps_e, eps_c, W["pair_classifier.weight"], W["pair_classifier.bias"], self.opt.ec_dim)
+        return (prob, (eps_e, eps_c)) if return_noise else prob
+
+    def draw_counts(self, lat, labels, n_draws, groups=None, noise=None, return_noise=False, n_groups=None):
+        """int64 [K, G, 3]: TP / FP / FN of `prob > 0.5` (numpy's .round() of a probability, ref :282: exactly 0.5 predicts 0) against
+        `labels == 1`, per noise draw and group, without materialising the [K, N] probabilities (extension; the case analysis'
+        re-evaluation loop, mmd_wommd_case_analysis.py:662-696).  groups: int [N] ids in [0, G), G <= 8 (default: one group);
+        n_groups: G when the highest id is unused (default max id + 1).  The overall counts are the sum over groups."""
+        self._require_cuda()
+        dev = lat.device
+        N = lat.shape[0]
+        labels = torch.as_tensor(labels).to(dev, torch.float32).reshape(-1).contiguous()
+        if labels.numel() != N:
+            raise L.CarelError("draw_counts: one label per row of lat")
+        G = 1 if n_groups is None else int(n_groups)
+        if groups is not None:
+            groups = torch.as_tensor(groups).reshape(-1)
+            if groups.numel() != N or groups.dtype.is_floating_point:
+                raise L.CarelError("draw_counts: groups must be N integer ids")
+            lo, hi = int(groups.min()), int(groups.max())           # checked on the host before any launch
+            if n_groups is None:
+                G = hi + 1
+            if lo < 0 or hi >= G:
+                raise L.CarelError("draw_counts: group ids must be in [0, %d)" % G)
+            groups = groups.to(dev, torch.int32).contiguous()
+        if not 1 <= G <= ops.PAIR_DRAWS_MAX_GROUPS:
+            raise L.CarelError("draw_counts: between 1 and %d groups" % ops.PAIR_DRAWS_MAX_GROUPS)
+        eps_e, eps_c = self._draws_noise(dev, n_draws, noise)
+        W, _ = self._tail_weights()
+        _, counts = ops.pair_probs_draws(lat, eps_e, eps_c, W["pair_classifier.weight"], W["pair_classifier.bias"], self.opt.ec_dim,
+                                         labels=labels, groups=groups, n_groups=G, want_prob=False)
+        counts = counts.to(torch.int64)
+        return (counts, (eps_e, eps_c)) if return_noise else counts
+
+    def get_pair_preds(self, input_ids, att_masks, token_type_ids, round=True):
+        """Reference `get_pair_preds` (:265-282): nested python list [[0.|1.], ...]; round=False (newsplit script :442-480): the
+        probabilities in the same nesting."""
+        prob = self.pair_probabilities(input_ids, att_masks, token_type_ids).reshape(-1, 1).cpu().detach().numpy()
+        return (prob.round() if round else prob).tolist()
 
     # reference helper kept for callers that use it directly (:515-523)
     def get_annealed_weight(self, iteration, lambda_weight):

@@ -530,3 +530,8 @@ class DrlClassifier(_Base):
         raise L.CarelError("the approximation network belongs to drl_classifier_ec_vi")
 
     get_ec_upper_loss = get_ec_aprx_loss
+
+    def pair_latents(self, *a, **k):
+        raise L.CarelError("pair_latents / pair_probabilities_from / draw_counts cover the two-space models; this model has pair_logits")
+
+    pair_probabilities_from = draw_counts = pair_latents

@@ -423,6 +423,40 @@ def pair_probs(lat, eps_e, eps_c, pair_w, pair_b, D):
     return prob
 
 
+PAIR_DRAWS_MAX_GROUPS = 8
+
+
+def pair_probs_draws(lat, eps_e, eps_c, pair_w, pair_b, D, labels=None, groups=None, n_groups=1, want_prob=True, counts_out=None):
+    """carel_pair_probs_draws: K = eps_e.shape[0] noise draws over the same latents.  Returns (prob [K, N] f32 or None,
+    counts [K, n_groups, 3] int32 = TP / FP / FN or None -- counted when `labels` is given).  labels: f32 [N]; groups: int32 [N]
+    whose ids the CALLER has checked to be in [0, n_groups) (a row outside is counted nowhere)."""
+    _chk_cuda(lat, eps_e, eps_c)
+    N, K = lat.shape[0], eps_e.shape[0]
+    if (eps_e.dtype != torch.float32 or eps_c.dtype != torch.float32 or tuple(eps_e.shape) != (K, D) or tuple(eps_c.shape) != (K, D)
+            or not eps_e.is_contiguous() or not eps_c.is_contiguous()):
+        raise L.CarelError("pair_probs_draws: eps_e and eps_c must be contiguous float32 [n_draws, ec_dim]")
+    if lat.dtype != torch.float32 or lat.dim() != 2 or lat.shape[1] != 4 * D or not lat.is_contiguous():
+        raise L.CarelError("pair_probs_draws: lat must be contiguous float32 [N, 4 * ec_dim]")
+    prob = torch.empty((K, N), device=lat.device, dtype=torch.float32) if want_prob else None
+    counts = None
+    if labels is not None:
+        _chk_cuda(labels)
+        if labels.dtype != torch.float32 or labels.numel() != N or not labels.is_contiguous():
+            raise L.CarelError("pair_probs_draws: labels must be contiguous float32 [N]")
+        if groups is not None:
+            _chk_cuda(groups)
+            if groups.dtype != torch.int32 or groups.numel() != N or not groups.is_contiguous():
+                raise L.CarelError("pair_probs_draws: groups must be contiguous int32 [N]")
+        counts = counts_out if counts_out is not None else torch.empty((K, n_groups, 3), device=lat.device, dtype=torch.int32)
+        if counts.dtype != torch.int32 or counts.numel() != K * n_groups * 3 or not counts.is_contiguous() or not counts.is_cuda:
+            raise L.CarelError("pair_probs_draws: counts must be a contiguous int32 [n_draws, n_groups, 3] device tensor")
+    L.check(L.load().carel_pair_probs_draws(lat.data_ptr(), eps_e.data_ptr(), eps_c.data_ptr(), pair_w.data_ptr(), pair_b.data_ptr(), N, D, K,
+                                            None if prob is None else prob.data_ptr(), None if labels is None else labels.data_ptr(),
+                                            None if groups is None else groups.data_ptr(), int(n_groups),
+                                            None if counts is None else counts.data_ptr(), L.current_stream()), "carel_pair_probs_draws")
+    return prob, counts
+
+
 def _hsic_args(x, y, s_x, s_y):
     _chk_cuda(x, y)
     if x.shape != y.shape or x.dtype != torch.float32 or y.dtype != torch.float32 or x.stride(1) != 1 or y.stride(1) != 1:

@@ -87,24 +87,54 @@ def save_ckp(state, ckpt_path, model_id="carel"):
     torch.save({k: v.detach().cpu().clone() for k, v in state.items()}, os.path.join(ckpt_path, model_id + ".pt"))
 
 
-def generate_self_train_data(test_docs_pair_size, test_df, test_loader, model, strategy, device="cuda"):
-    """ref :734-799: pseudo-label the test documents (top pair positive, random / extreme / thresholded negative)."""
+def prf_from_counts(counts):
+    """(precision, recall, F1) from TP / FP / FN counts in the last dimension (`DrlClassifier.draw_counts`: [K, G, 3]; sum over the
+    groups first for the overall figures), as float64 tensors of the leading shape, with sklearn's binary semantics: 0 where a
+    denominator is 0 (ref :868-870)."""
+    c = torch.as_tensor(counts).to(torch.float64)
+    tp, fp, fn = c[..., 0], c[..., 1], c[..., 2]
+    zero = torch.zeros_like(tp)
+    prec = torch.where(tp + fp > 0, tp / (tp + fp).clamp(min=1), zero)
+    rec = torch.where(tp + fn > 0, tp / (tp + fn).clamp(min=1), zero)
+    f1 = torch.where(prec + rec > 0, 2 * prec * rec / (prec + rec).clamp(min=1e-300), zero)
+    return prec, rec, f1
+
+
+def generate_self_train_data(test_docs_pair_size, test_df, test_loader, model, strategy, self_training_iteration=None, r_flag=None,
+                             device="cuda"):
+    """ref :734-799: pseudo-label the test documents (top pair positive, random / extreme / thresholded negative).
+    With the new-split script's two extra arguments (drl_classifier_ec_mmd_final_mul_newsplit_emnlp.py :961-1064) also its strategies:
+    "temporal_order" takes as positive the first pair, in descending stable order of the scores, whose `temporal_order` is true and as
+    negative a random pair after it; "temporal_order_modification" is "temporal_order" at self-training iteration 0 and "random"
+    afterwards.  r_flag "true" asks get_pair_preds for rounded predictions, except that "temporal_order_modification" at iteration 0
+    ranks the probabilities themselves (:965-969).  r_flag None (the older scripts' call) calls get_pair_preds(ids, att, tt) as before."""
     predicted_df = test_df.copy()
     model.eval()
+    if strategy in ("temporal_order", "temporal_order_modification") and "temporal_order" not in predicted_df.columns:
+        raise ValueError("strategy %r needs the `temporal_order` column of read_ECPE_data(..., newsplit=True)" % strategy)
+    if strategy == "temporal_order_modification" and self_training_iteration is None:
+        raise ValueError("strategy 'temporal_order_modification' needs self_training_iteration")
+    round_flag = r_flag == "true"
+    if strategy == "temporal_order_modification" and self_training_iteration < 1:
+        round_flag = False
     with torch.no_grad():
         for data in test_loader:
             ids = data["input_ids"].to(device, dtype=torch.long)
             att = data["attention_masks"].to(device, dtype=torch.long)
             tt = data["token_type_ids"].to(device, dtype=torch.long)
-            outs = model.get_pair_preds(ids, att, tt)
+            outs = model.get_pair_preds(ids, att, tt) if r_flag is None else model.get_pair_preds(ids, att, tt, round_flag)
             if torch.is_tensor(outs):        # drl_classifier_en.py:826-828: raw logits -> probabilities
                 outs = torch.sigmoid(outs).cpu().detach().numpy().tolist()
             predicted_df["label"] = [x[0] for x in outs]
     rows, curr = [], 0
     for doc_pair_size in test_docs_pair_size:
+        if doc_pair_size == 0:               # (:984-985)
+            continue
         max_pos, max_neg = float("-inf"), float("-inf")
         pos_pair = pos_emotion = neg_pair = neg_emotion = None
         prob_dict = {}
+        if strategy == "temporal_order_modification":      # rewritten on the first document, for all of them (:996-1000)
+            strategy = "random" if self_training_iteration >= 1 else "temporal_order"
         for i in range(doc_pair_size):
             index = i + curr
             row = predicted_df.iloc[index]
@@ -127,6 +157,19 @@ def generate_self_train_data(test_docs_pair_size, test_df, test_loader, model, s
                     neg_pair, neg_emotion = other["pair"], other["emotion"]
                 else:               # "extreme" carries no emotion column values (ref :789-793 leaves both None), and a one-pair
                     neg_pair = predicted_df.iloc[srt[-1][0]]["pair"]     # document yields that pair as positive AND negative
+            elif strategy == "temporal_order":
+                prob_dict[index] = prob
+        if strategy == "temporal_order":    # (:1035-1051) no ordered pair, or the ordered pair last: the document yields nothing
+            srt = sorted(prob_dict.items(), key=lambda x: x[1], reverse=True)
+            index_ = None
+            for index_, (key, _) in enumerate(srt):
+                top = predicted_df.iloc[key]
+                if top["temporal_order"]:
+                    pos_pair, pos_emotion = top["pair"], top["emotion"]
+                    break
+            if index_ is not None and index_ < len(srt) - 1:
+                other = predicted_df.iloc[srt[randint(index_ + 1, len(srt) - 1)][0]]
+                neg_pair, neg_emotion = other["pair"], other["emotion"]
         curr += doc_pair_size
         if pos_pair is not None and neg_pair is not None:
             rows.append((pos_pair, 1, pos_emotion))

@@ -545,6 +545,17 @@ int carel_scale_f32(void* x_f32, int64_t n, const void* scale_dev_f32, void* str
 int64_t carel_tail_pair_dead_offset(int32_t batch, int32_t ec_dim, int32_t bow_dim);
 int carel_pair_probs(const void* lat, const void* eps_e, const void* eps_c, const void* pair_w, const void* pair_b,
                      int32_t batch, int32_t ec_dim, void* prob, void* stream);
+/* carel_pair_probs for n_draws noise vectors over the same latents (the case analysis re-evaluates the test set with fresh noise until
+ * its F1 crosses a threshold, mmd_wommd_case_analysis.py:662-696; in eval mode only eps changes between draws).
+ *   lat [n, 4*ec_dim] f32, eps_e / eps_c [n_draws, ec_dim] f32, pair_w [2*ec_dim], pair_b [1]
+ *   prob    f32 [n_draws, n] or NULL; every entry has the bits carel_pair_probs gives for that draw's eps
+ *   labels  f32 [n] (positive: == 1) or NULL; groups int32 [n] in [0, n_groups) or NULL (all rows in group 0); n_groups in 1..8
+ *   counts  int32 [n_draws, n_groups, 3] = TP, FP, FN with the prediction prob > 0.5, or NULL; needs labels; written in full by the
+ *           call (no pre-zeroing); a row whose group id is outside [0, n_groups) is counted nowhere
+ * At least one of prob / counts; ec_dim in 1..32; n, n_draws >= 1.  Integer counting only: the same bits on every launch. */
+int carel_pair_probs_draws(const void* lat, const void* eps_e, const void* eps_c, const void* pair_w, const void* pair_b,
+                           int32_t n, int32_t ec_dim, int32_t n_draws, void* prob, const void* labels, const void* groups,
+                           int32_t n_groups, void* counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Sentence adapters (ABI 8) of drl_classifier_ec_mmd_final_mul_emnlp.py / ..._newsplit_emnlp.py: the emotion and the cause latent
