@@ -6,6 +6,7 @@ forward (encoder + VAE tail -> scalar loss); its backward enqueues the HIP backw
 gradients in a flat fp32 buffer that every `Parameter.grad` aliases.  There is no eager/CPU fallback:
 calling the model with CPU tensors raises.
 """
+import contextlib
 import ctypes as C
 import math
 import os
@@ -686,6 +687,19 @@ class DrlClassifier(nn.Module):
         """Called by the fused optimiser, which rewrites the bf16 shadow itself."""
         self._shadow_versions = self._versions()
 
+    def _weights_ready(self):
+        """Before an encoder pass: wait for weight updates still in flight on the auxiliary stream, bring the bf16 shadow up to date."""
+        if self._adam_hook is not None:
+            self._adam_hook._join()
+        self._refresh_shadow()
+
+    def _cached(self, key, make):
+        """The small per-shape buffer stored under `key` in self._ws, built by make() on first use."""
+        buf = self._ws.get(key)
+        if buf is None:
+            buf = self._ws[key] = make()
+        return buf
+
     def _w(self, key, bf16=False):
         off = self._offs[key]
         base = self._shadow if bf16 else self._flat
@@ -731,14 +745,11 @@ class DrlClassifier(nn.Module):
         """The fp32 debug forward: returns the final hidden states f32 [Bp*S, 768] (dense rows)."""
         lib = L.load()
         dev = self._flat.device
-        key = ("f32", c.Bp, c.S)
-        buf = self._ws.get(key)
-        if buf is None:
-            buf = SimpleNamespace(work=torch.zeros(lib.carel_encoder_f32_work_bytes(c.Bp, c.S), device=dev, dtype=torch.uint8),
-                                  x=torch.zeros((c.Bp * c.S, H), device=dev, dtype=torch.float32),
-                                  dummy=SimpleNamespace(act=torch.zeros(256, device=dev, dtype=torch.uint8), scratch=None))
-            self._ws[key] = buf
-        ea = self._encoder_args(c.ids, c.att, c.tt, buf.dummy, c.Bp, c.S, True, False, 0, 0, None, None)
+        buf = self._cached(("f32", c.Bp, c.S), lambda: SimpleNamespace(
+            work=torch.zeros(lib.carel_encoder_f32_work_bytes(c.Bp, c.S), device=dev, dtype=torch.uint8),
+            x=torch.zeros((c.Bp * c.S, H), device=dev, dtype=torch.float32),
+            dummy=SimpleNamespace(act=torch.zeros(256, device=dev, dtype=torch.uint8), scratch=None)))
+        ea =self._encoder_args(c.ids, c.att, c.tt, buf.dummy, c.Bp, c.S, True, False, 0, 0, None, None)
         F = self._layer_arrays_f32()
         ea.layers = C.cast(F, C.POINTER(L.LayerParams))
         L.check(lib.carel_encoder_forward_f32(C.byref(ea), buf.work.data_ptr(), buf.x.data_ptr(), L.current_stream()), "carel_encoder_forward_f32")
@@ -771,13 +782,12 @@ class DrlClassifier(nn.Module):
         if not self.cls_only_last or self.adapter != "false":        # an adapter reads every row of the last layer
             return None
         n_cls = (Bp + 127) // 128 * 128
-        key = ("cls", B, Bp, S)
-        base = self._ws.get(key)
-        if base is None:
+
+        def make():
             orig = np.full(n_cls, -1, dtype=np.int32)
             orig[:B] = np.arange(B, dtype=np.int32) * S
-            base = SimpleNamespace(orig=torch.from_numpy(orig).to(dev), compact=torch.arange(B, dtype=torch.int32, device=dev))
-            self._ws[key] = base
+            return SimpleNamespace(orig=torch.from_numpy(orig).to(dev), compact=torch.arange(B, dtype=torch.int32, device=dev))
+        base = self._cached(("cls", B, Bp, S), make)
         if pack is None:
             rows = base.orig                      # dense: the [CLS] token of sample i sits at row i*S
         else:
@@ -920,6 +930,61 @@ class DrlClassifier(nn.Module):
         return SimpleNamespace(n_tokens=t_pad, t_eff=t_eff, cu=torch.from_numpy(cu).to(dev, non_blocking=True),
                                tok_row=torch.from_numpy(tok).to(dev, non_blocking=True))
 
+    def _prepare_inputs(self, input_ids, att_masks, token_type_ids, seq_lengths=None):
+        """How a batch gets to the encoder, for every model path: a call record with B (real samples), S and Bp (the length and batch the
+        encoder runs: _padded_shape), ids / att / tt padded to [Bp, S] (_prep_ids) and the token packing (_pack_info; None = dense).
+        Works on the tensors' own device; with seq_lengths given nothing is read back."""
+        c = _Call()
+        c.B, S = input_ids.shape
+        c.Bp, c.S = self._padded_shape(c.B, S)
+        c.ids, c.att = self._prep_ids(input_ids, c.Bp, c.S, self.cfg.pad_id), self._prep_ids(att_masks, c.Bp, c.S)
+        c.tt = None if token_type_ids is None else self._prep_ids(token_type_ids, c.Bp, c.S)
+        c.pack = self._pack_info(c.att, c.B, c.Bp, c.S, seq_lengths)
+        return c
+
+    def _run_encoder(self, c, training, train_drop, seed, row_offset, want_cls=True, weights_ready=False):
+        """The one bf16 encoder pass over a prepared record (_prepare_inputs): records c.ws, c.cls (the [CLS] compaction; None without
+        want_cls or where _cls_info declines) and c.ea, and returns (x_last_ptr, cls_rows, n_rows): where a reader of the last layer
+        finds sample i -- compact [CLS] rows, else the packed sample starts, else dense (None: row i*S) -- and how many rows there are.
+        weights_ready: the caller has brought the bf16 shadow up to date itself (the chunk loops do it once, before the first chunk)."""
+        if not weights_ready:
+            self._weights_ready()
+        lib = L.load()
+        c.ws = self._workspace(c.Bp, c.S, inference=not training)
+        c.cls = self._cls_info(c.B, c.Bp, c.S, c.pack, self._flat.device) if want_cls else None
+        c.ea = self._encoder_args(c.ids, c.att, c.tt, c.ws, c.Bp, c.S, not training, train_drop, seed, row_offset, c.pack, c.cls)
+        L.check(lib.carel_encoder_forward(C.byref(c.ea), L.current_stream()), "carel_encoder_forward")
+        x_last_ptr = lib.carel_encoder_x_last(C.byref(c.ea))
+        if c.cls is not None:
+            return x_last_ptr, c.cls.compact, c.cls.n_cls
+        if c.pack is not None:
+            return x_last_ptr, c.pack.cu, c.pack.n_tokens
+        return x_last_ptr, None, c.Bp * c.S
+
+    def _next_seed(self):
+        """The dropout seed of the next forward call (every mask of one call derives from it)."""
+        self._fwd_count += 1
+        return (self.dropout_base_seed * 1000003 + self._fwd_count) & 0xFFFFFFFF
+
+    def _tail_buffers(self, c):
+        return self._cached(("tail", c.B, c.S), lambda: ops.TailBuffers(c.B, c.S, self.opt.ec_dim, self.opt.e_num_class, self.opt.pair_bow_dim,
+                                                                        c.ids.device, rows=c.Bp * c.S))
+
+    @contextlib.contextmanager
+    def _overwriting_grads(self, accumulate, lo=0, hi=None, keep=None):
+        """Around a backward that overwrites [lo, hi) of the flat gradient buffer (default: all of it).  accumulate: the caller's answer
+        to "do these parameters already hold a gradient?"; then what the range held is set aside and added back afterwards, as
+        autograd accumulates.  keep = (klo, khi): a sub-range the backward leaves alone, which must not be added to itself.  Yields
+        accumulate; the caller binds the .grad views when the block is done."""
+        prev = None
+        if accumulate:
+            prev = self._flat_grad[lo:hi].clone()
+            if keep is not None:
+                prev[keep[0] - lo:keep[1] - lo].zero_()
+        yield accumulate
+        if accumulate:
+            self._flat_grad[lo:hi].add_(prev)
+
     def set_noise(self, eps_e, eps_c):
         """Test hook: use these two [ec_dim] vectors as the next call's reparameterisation noise (ref :350)."""
         self._noise = None if eps_e is None else (eps_e, eps_c)
@@ -941,25 +1006,21 @@ class DrlClassifier(nn.Module):
                    seq_lengths=None):
         self._require_cuda()
         ops._chk_cuda(input_ids, att_masks, token_type_ids, content_bow)
-        B, S = input_ids.shape
-        Bp, S = self._padded_shape(B, S)
-        c = _Call()
-        c.B, c.S, c.Bp = B, S, Bp
-        c.ids, c.att = self._prep_ids(input_ids, Bp, S, self.cfg.pad_id), self._prep_ids(att_masks, Bp, S)
-        c.tt = None if token_type_ids is None else self._prep_ids(token_type_ids, Bp, S)
+        B = input_ids.shape[0]
+        self._padded_shape(*input_ids.shape)         # a length the encoder refuses is refused before anything is drawn or counted
         dev = input_ids.device
         f32 = torch.float32
-        c.labels = dict(emo=emotion_labels.to(dev, torch.long).reshape(-1).contiguous(), cau=cause_labels.to(dev, f32).reshape(-1).contiguous(),
-                        pair=pair_labels.to(dev, f32).reshape(-1).contiguous(), bow=content_bow.to(dev, f32).contiguous())
-        if c.labels["bow"].shape != (B, self.opt.pair_bow_dim):
+        labels = dict(emo=emotion_labels.to(dev, torch.long).reshape(-1).contiguous(), cau=cause_labels.to(dev, f32).reshape(-1).contiguous(),
+                      pair=pair_labels.to(dev, f32).reshape(-1).contiguous(), bow=content_bow.to(dev, f32).contiguous())
+        if labels["bow"].shape != (B, self.opt.pair_bow_dim):
             raise L.CarelError("content_bow must be [batch, pair_bow_dim]")
-        c.iteration = int(iteration)
-        c.training = training
-        c.eps_e, c.eps_c = self._draw_noise(dev)
-        self._fwd_count += 1
-        c.seed = (self.dropout_base_seed * 1000003 + self._fwd_count) & 0xFFFFFFFF
+        eps = self._draw_noise(dev)
+        seed = self._next_seed()
+        # after the launches above: the packing arrays go to the device in host-to-device copies, which the host may have to wait for
+        c = self._prepare_inputs(input_ids, att_masks, token_type_ids, seq_lengths)
+        c.labels, c.iteration, c.training, c.seed = labels, int(iteration), training, seed
+        c.eps_e, c.eps_c = eps
         c.row_offset = 0 if self._dp is None else self._dp.row_offset(B)
-        c.pack = self._pack_info(c.att, B, Bp, S, seq_lengths)
         if self.adapter != "false" and self._dp is not None:
             raise L.CarelError("sentence adapters are not supported under DataParallel")
         if self._gan:
@@ -969,12 +1030,7 @@ class DrlClassifier(nn.Module):
             if c.labels["emo_f"].numel() != B or c.labels["cau"].numel() != B:
                 raise L.CarelError("emotion_labels and cause_labels must hold one value per pair")
         self._check_tail_batch(B)
-        key = ("tail", B, S)
-        buf = self._ws.get(key)
-        if buf is None:
-            buf = ops.TailBuffers(B, S, self.opt.ec_dim, self.opt.e_num_class, self.opt.pair_bow_dim, dev, rows=Bp * S)
-            self._ws[key] = buf
-        c.buf = buf
+        c.buf = self._tail_buffers(c)
         if self._dp is not None:
             self._dp.prepare(c)
         return c
@@ -1034,41 +1090,28 @@ class DrlClassifier(nn.Module):
         of the queries or adapter weights by any route -- load_state_dict, an in-place edit, a write through .data -- takes effect."""
         dev = self._flat.device
         G = self.head_number if self.adapter == "raw" else 1
-        key = ("adapter", c.B, c.S)
-        buf = self._ws.get(key)
-        if buf is None:
-            buf = self._ws[key] = ops.AdapterBuffers(c.B, c.S, G, dev)
+        buf = self._cached(("adapter", c.B, c.S), lambda: ops.AdapterBuffers(c.B, c.S, G, dev))
         qs = [getattr(self, n).to(dev, torch.float32).reshape(-1).contiguous() for n in ("emotion_q", "cause_q")]
         if qs[0].numel() != H or qs[1].numel() != H:
             raise L.CarelError("emotion_q / cause_q must hold 768 values")
-        u = self._ws.get("adapter_u")
-        if u is None:
-            u = self._ws["adapter_u"] = torch.empty((2, G, H), device=dev, dtype=torch.float32)
+        u = self._cached("adapter_u", lambda: torch.empty((2, G, H), device=dev, dtype=torch.float32))
         a = ops.adapter_args(self.adapter, G, qs, self._adapter_weights(), u, buf, c.Bp, x=SimpleNamespace(data_ptr=lambda: x_last_ptr))
         ops.adapter_build_u(a)
         ops.adapter_forward(a)
         return a, buf
 
     def _run_forward(self, c, training):
-        if self._adam_hook is not None:
-            self._adam_hook._join()          # weight updates still in flight on the auxiliary stream
-        self._refresh_shadow()
         train_drop = self.training          # dropout follows module mode (model.train() / .eval()), like nn.Dropout
-        lib = L.load()
-        st = L.current_stream()
         if self.debug_fp32:
+            self._weights_ready()
             if training:
                 raise L.CarelError("debug_fp32 is a forward-only measurement mode: call forward_terms() / forward() under torch.no_grad()")
             train_drop = False
-            c.pack, c.cls, ws = None, None, None
-            ea, x_f32 = self._run_encoder_fp32(c)
-            x_last_ptr = x_f32.data_ptr()
+            c.pack, c.cls, c.ws = None, None, None
+            c.ea, x_f32 = self._run_encoder_fp32(c)
+            x_last_ptr, cls_rows, n_rows = x_f32.data_ptr(), None, c.Bp * c.S
         else:
-            ws = self._workspace(c.Bp, c.S, inference=not training)
-            c.cls = self._cls_info(c.B, c.Bp, c.S, c.pack, self._flat.device)
-            ea = self._encoder_args(c.ids, c.att, c.tt, ws, c.Bp, c.S, not training, train_drop, c.seed, c.row_offset, c.pack, c.cls)
-            L.check(lib.carel_encoder_forward(C.byref(ea), st), "carel_encoder_forward")
-            x_last_ptr = lib.carel_encoder_x_last(C.byref(ea))
+            x_last_ptr, cls_rows, n_rows = self._run_encoder(c, training, train_drop, c.seed, c.row_offset)
         W, G = self._tail_weights()
         xl = SimpleNamespace(data_ptr=lambda: x_last_ptr)
         c.ad = None
@@ -1078,10 +1121,6 @@ class DrlClassifier(nn.Module):
             head_in, d_head_in = abuf.out, abuf.d_out
         klw = ops.kl_anneal_weight(c.iteration, self.opt)
         drop = (self.opt.dropout if train_drop else 0.0, c.seed, c.row_offset)
-        if c.cls is not None:           # compact final hidden states: sample i's [CLS] is row i
-            cls_rows, n_rows = c.cls.compact, c.cls.n_cls
-        else:
-            cls_rows, n_rows = (None, c.Bp * c.S) if c.pack is None else (c.pack.cu, c.pack.n_tokens)
         ta = ops.tail_args(c.buf, xl, W, c.labels, c.eps_e, c.eps_c, self.opt, klw, grads=G, drop=drop, cls_rows=cls_rows, n_rows=n_rows,
                            head_in=head_in, d_head_in=d_head_in)
         ops.tail_latents(ta)
@@ -1091,14 +1130,11 @@ class DrlClassifier(nn.Module):
         ops.tail_losses(ta)
         if self._gan:                                    # the two adversaries on the z the tail has written; terms[4] = the script's vae loss
             c.gan_terms = self._gan_disc(c, drop)
-        c.ea, c.ta, c.ws = ea, ta, ws
+        c.ta = ta
         c.keep = (W, G, xl)
 
     def _gan_disc(self, c, drop):
-        key = ("gan_terms", c.B, c.S)
-        terms = self._ws.get(key)
-        if terms is None:
-            terms = self._ws[key] = torch.zeros(8, device=self._flat.device, dtype=torch.float32)
+        terms = self._cached(("gan_terms", c.B, c.S), lambda: torch.zeros(8, device=self._flat.device, dtype=torch.float32))
 
         def img(i, k):
             o = self._offs[k] - self._disc_lo
@@ -1144,40 +1180,33 @@ class DrlClassifier(nn.Module):
             self._run_backward(c, go, None)
 
     def _run_backward(self, c, grad_out, grad_z=None):
-        lib = L.load()
-        st = L.current_stream()
-        named = self._named
-        first = named[self._order[0]]
-        accumulate = first.grad is not None
-        prev = self._flat_grad.clone() if accumulate else None
-        if accumulate and self._gan:         # the adversaries' range is not rewritten below: it must not be added to itself
-            prev[self._disc_lo:self._disc_hi].zero_()
-        go = grad_out.to(torch.float32).reshape(1).contiguous()      # device scalar, never read on the host
-        ea = c.ea
-        ea.dx = c.buf.dx_last.data_ptr()          # [Bp*S (or packed n_tokens), 768]; cleared + CLS rows written by the tail backward
-        ops.tail_backward(c.ta, go, None if grad_z is None else grad_z.to(torch.float32).contiguous())
-        if c.ad is not None:                     # adapter mode: d head_in -> every row of dx_last (the tail left dx_last alone)
-            c.ad.dx_f32 = ea.dx
-            ops.adapter_backward(c.ad)
-            if self._adapter_train_names:        # opt.train_adapter: overwritten like every gradient of this call (`prev` is added below)
-                ops.adapter_backward_weights(c.ad, ops.adapter_wgrad_args(self._ws[("adapter", c.B, c.S)], self._adapter_grads()))
-        # classifier / decoder gradients were produced for grad_output = 1: one contiguous range of the flat buffer
-        lo = self._offs["decoder.weight"]
-        ops.scale_(self._flat_grad[lo:self._pair_hi], go)
-        if self._dp is not None:
-            self._dp.tail_done()
-        self._backward_encoder(ea, accumulate)
-        if c.ad is not None:
-            # the adapters read padded positions, so for once they carry gradient; HF's embeddings have padding_idx = pad_id (word table,
-            # and RoBERTa's position table, whose padded positions take position pad_id): that row gets none
-            e = "encoder.embeddings."
-            self._grad_view(e + "word_embeddings.weight")[self.cfg.pad_id].zero_()
-            if self.cfg.roberta:
-                self._grad_view(e + "position_embeddings.weight")[self.cfg.pad_id].zero_()
-        if self._dp is not None:
-            self._dp.backward_done(None if accumulate else self._adam_hook)
-        if accumulate:
-            self._flat_grad.add_(prev)
+        # the adversaries' range is not rewritten below: it must not be added to itself
+        keep = (self._disc_lo, self._disc_hi) if self._gan else None
+        with self._overwriting_grads(self._group_has_grad("vae"), keep=keep) as accumulate:
+            go = grad_out.to(torch.float32).reshape(1).contiguous()      # device scalar, never read on the host
+            ea = c.ea
+            ea.dx = c.buf.dx_last.data_ptr()          # [Bp*S (or packed n_tokens), 768]; cleared + CLS rows written by the tail backward
+            ops.tail_backward(c.ta, go, None if grad_z is None else grad_z.to(torch.float32).contiguous())
+            if c.ad is not None:                     # adapter mode: d head_in -> every row of dx_last (the tail left dx_last alone)
+                c.ad.dx_f32 = ea.dx
+                ops.adapter_backward(c.ad)
+                if self._adapter_train_names:        # opt.train_adapter: overwritten like every gradient of this call
+                    ops.adapter_backward_weights(c.ad, ops.adapter_wgrad_args(self._ws[("adapter", c.B, c.S)], self._adapter_grads()))
+            # classifier / decoder gradients were produced for grad_output = 1: one contiguous range of the flat buffer
+            lo = self._offs["decoder.weight"]
+            ops.scale_(self._flat_grad[lo:self._pair_hi], go)
+            if self._dp is not None:
+                self._dp.tail_done()
+            self._backward_encoder(ea, accumulate)
+            if c.ad is not None:
+                # the adapters read padded positions, so for once they carry gradient; HF's embeddings have padding_idx = pad_id (word table,
+                # and RoBERTa's position table, whose padded positions take position pad_id): that row gets none
+                e = "encoder.embeddings."
+                self._grad_view(e + "word_embeddings.weight")[self.cfg.pad_id].zero_()
+                if self.cfg.roberta:
+                    self._grad_view(e + "position_embeddings.weight")[self.cfg.pad_id].zero_()
+            if self._dp is not None:
+                self._dp.backward_done(None if accumulate else self._adam_hook)
         self._bind_grads()
         if self.strict_pair_skip and self._has_pair_skip and not accumulate:
             # stock optimisers: leave pair_classifier.grad None when the pair loss was replaced by 0, exactly as the reference
@@ -1307,39 +1336,22 @@ class DrlClassifier(nn.Module):
         `pair_probabilities_from` / `draw_counts` then evaluate any number of noise draws on it without another encoder pass."""
         self._require_cuda()
         ops._chk_cuda(input_ids, att_masks, token_type_ids)
-        dev = input_ids.device
-        N, S0 = input_ids.shape
-        out = torch.empty((N, 4 * self.opt.ec_dim), device=dev, dtype=torch.float32)
+        N = input_ids.shape[0]
+        out = torch.empty((N, 4 * self.opt.ec_dim), device=input_ids.device, dtype=torch.float32)
         self._refresh_shadow()
-        lib = L.load()
         for s in range(0, N, chunk):
-            ids = input_ids[s:s + chunk]
-            B = ids.shape[0]
-            Bp, S = self._padded_shape(B, S0)
-            ids = self._prep_ids(ids, Bp, S, self.cfg.pad_id)
-            att = self._prep_ids(att_masks[s:s + chunk], Bp, S)
-            tt = None if token_type_ids is None else self._prep_ids(token_type_ids[s:s + chunk], Bp, S)
-            ws = self._workspace(Bp, S, inference=True)
-            pack = self._pack_info(att, B, Bp, S)
-            cls = self._cls_info(B, Bp, S, pack, dev)
-            ea = self._encoder_args(ids, att, tt, ws, Bp, S, True, False, 0, 0, pack, cls)
-            L.check(lib.carel_encoder_forward(C.byref(ea), L.current_stream()), "carel_encoder_forward")
-            x_last_ptr = lib.carel_encoder_x_last(C.byref(ea))
-            key = ("tail", B, S)
-            buf = self._ws.get(key)
-            if buf is None:
-                buf = ops.TailBuffers(B, S, self.opt.ec_dim, self.opt.e_num_class, self.opt.pair_bow_dim, dev, rows=Bp * S)
-                self._ws[key] = buf
+            c = self._prepare_inputs(input_ids[s:s + chunk], att_masks[s:s + chunk], None if token_type_ids is None else token_type_ids[s:s + chunk])
+            x_last_ptr, cls_rows, _ = self._run_encoder(c, False, False, 0, 0, weights_ready=True)
+            buf = self._tail_buffers(c)
             W, _ = self._tail_weights()
             head_in = None
             if self.adapter != "false":
-                _, abuf = self._adapter_forward(SimpleNamespace(B=B, Bp=Bp, S=S), x_last_ptr)
+                _, abuf = self._adapter_forward(c, x_last_ptr)
                 head_in = abuf.out
-            ta = ops.tail_args(buf, SimpleNamespace(data_ptr=lambda: x_last_ptr), W, None, None, None, self.opt, 1.0,
-                               cls_rows=cls.compact if cls is not None else (None if pack is None else pack.cu), head_in=head_in)
-            ta._keep = (pack, cls)
+            ta = ops.tail_args(buf, SimpleNamespace(data_ptr=lambda: x_last_ptr), W, None, None, None, self.opt, 1.0, cls_rows=cls_rows,
+                               head_in=head_in)
             ops.tail_latents(ta)
-            out[s:s + B] = buf.lat
+            out[s:s + c.B] = buf.lat
         return out
 
     def _draws_noise(self, dev, n_draws, noise):
@@ -1463,7 +1475,8 @@ class FusedAdam:
         for p in (self.model._named.values() if self._clear_all else self._params):
             p.grad = None
 
-    def _launch(self, lo, hi, stream, with_skip):
+    def _adam_args(self, lo, hi):
+        """carel_adam_args of the coming step over the flat range [lo, hi): plain Adam, nothing skipped."""
         m = self.model
         a = L.AdamArgs()
         a.param, a.grad = m._flat.data_ptr() + 4 * lo, m._flat_grad.data_ptr() + 4 * lo
@@ -1473,6 +1486,11 @@ class FusedAdam:
         a.lr, a.beta1, a.beta2, a.eps = self.param_groups[0]["lr"], self.betas[0], self.betas[1], self.eps
         a.grad_scale = self.grad_scale
         a.skip_lo, a.skip_hi, a.skip_flag = 0, 0, None
+        return a
+
+    def _launch(self, lo, hi, stream, with_skip):
+        m = self.model
+        a = self._adam_args(lo, hi)
         call = getattr(m, "_last_call", None)
         if with_skip and m._has_pair_skip and call is not None and lo <= m._pair_lo and m._pair_hi <= hi:
             # the pair head keeps its weights/moments when its loss term was replaced by 0

@@ -31,7 +31,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from . import data as _data
-from .drl_classifier import DrlClassifier as _Base, FusedAdam, FusedRMSprop, H, _Call, _Holder, encoder_config  # noqa: F401 (FusedRMSprop: re-exported)
+from .drl_classifier import DrlClassifier as _Base, FusedAdam, FusedRMSprop, H, _Holder, encoder_config  # noqa: F401 (FusedRMSprop: re-exported)
 
 DEFAULT_OPT = dict(language="en", max_len=128, ec_num_class=1, pair_num_class=1, ec_dim=24, con_dim=384, pair_bow_dim=23771, bert_dim=768,
                    kl_ann_iterations=20000, epochs=10, batch_size=64, ec_kl_lambda=0.03, con_kl_lambda=0.03, label_smoothing=0.1,
@@ -262,40 +262,35 @@ class DrlClassifier(_Base):
                    seq_lengths=None):
         self._require_cuda()
         ops._chk_cuda(input_ids, att_masks, token_type_ids, content_bow)
-        B, S = input_ids.shape
-        Bp, S = self._padded_shape(B, S)
-        c = _Call()
-        c.B, c.S, c.Bp = B, S, Bp
-        c.ids, c.att = self._prep_ids(input_ids, Bp, S, self.cfg.pad_id), self._prep_ids(att_masks, Bp, S)
-        c.tt = None if token_type_ids is None else self._prep_ids(token_type_ids, Bp, S)
+        B = input_ids.shape[0]
+        self._padded_shape(*input_ids.shape)         # a length the encoder refuses is refused before anything is drawn or counted
         dev, f32 = input_ids.device, torch.float32
-        c.labels = dict(emo=emotion_labels.to(dev, f32).reshape(-1).contiguous(), cau=cause_labels.to(dev, f32).reshape(-1).contiguous(),
-                        pair=pair_labels.to(dev, f32).reshape(-1).contiguous(), bow=content_bow.to(dev, f32).contiguous())
-        if c.labels["bow"].shape != (B, self.opt.pair_bow_dim):
+        labels = dict(emo=emotion_labels.to(dev, f32).reshape(-1).contiguous(), cau=cause_labels.to(dev, f32).reshape(-1).contiguous(),
+                      pair=pair_labels.to(dev, f32).reshape(-1).contiguous(), bow=content_bow.to(dev, f32).contiguous())
+        if labels["bow"].shape != (B, self.opt.pair_bow_dim):
             raise L.CarelError("content_bow must be [batch, pair_bow_dim]")
-        c.iteration, c.training = int(iteration), training
-        c.eps = self._draw_noise_en(dev)
-        self._fwd_count += 1
-        c.seed = (self.dropout_base_seed * 1000003 + self._fwd_count) & 0xFFFFFFFF
-        c.row_offset = 0 if self._dp is None else self._dp.row_offset(B)
-        c.label_sum = None
+        eps = self._draw_noise_en(dev)
+        seed = self._next_seed()
+        label_sum = None
         if self._dp is not None:            # pos_weight (:599) of the GLOBAL batch: one float summed over ranks
-            c.label_sum = self._dp.all_reduce_sum(c.labels["pair"].sum().reshape(1))
-        c.pack = self._pack_info(c.att, B, Bp, S, seq_lengths)
-        key = ("en_tail", B, S)
-        buf = self._ws.get(key)
-        if buf is None:
+            label_sum = self._dp.all_reduce_sum(labels["pair"].sum().reshape(1))
+        # after the launches above: the packing arrays go to the device in host-to-device copies, which the host may have to wait for
+        c = self._prepare_inputs(input_ids, att_masks, token_type_ids, seq_lengths)
+        S, Bp = c.S, c.Bp
+        c.labels, c.iteration, c.training, c.eps, c.seed, c.label_sum = labels, int(iteration), training, eps, seed, label_sum
+        c.row_offset = 0 if self._dp is None else self._dp.row_offset(B)
+
+        def make():
             o = self.opt
-            lib = L.load()
             buf = SimpleNamespace(
                 pooled=torch.empty(B, H, device=dev), lat=torch.empty(B, 2 * o.con_dim + 4 * o.ec_dim, device=dev),
                 z=torch.empty(B, 2 * o.ec_dim + o.con_dim, device=dev), terms=torch.zeros(32, device=dev),
-                work=torch.empty(lib.carel_en_tail_workspace_floats(B, o.ec_dim, o.con_dim, o.pair_bow_dim), device=dev),
+                work=torch.empty(L.load().carel_en_tail_workspace_floats(B, o.ec_dim, o.con_dim, o.pair_bow_dim), device=dev),
                 dx_last=torch.empty(Bp * S, H, device=dev))
             if self.bow_loss:       # the site-120 copy of the content sample and the weight matrix [B, V]
                 buf.bow_work = ops.en_bow_workspace(B, o.con_dim, o.pair_bow_dim, dev)
-            self._ws[key] = buf
-        c.buf = buf
+            return buf
+        c.buf = self._cached(("en_tail", B, S), make)
         return c
 
     def _kl_weights(self, iteration):
@@ -350,27 +345,16 @@ class DrlClassifier(_Base):
         return a
 
     def _run_forward(self, c, training):
-        if self._adam_hook is not None:
-            self._adam_hook._join()
-        self._refresh_shadow()
         train_drop = self.training
-        ws = self._workspace(c.Bp, c.S, inference=not training)
-        c.cls = self._cls_info(c.B, c.Bp, c.S, c.pack, self._flat.device)
-        ea = self._encoder_args(c.ids, c.att, c.tt, ws, c.Bp, c.S, not training, train_drop, c.seed, c.row_offset, c.pack, c.cls)
+        x_last_ptr, cls_rows, n_rows = self._run_encoder(c, training, train_drop, c.seed, c.row_offset)
         lib, st = L.load(), L.current_stream()
-        L.check(lib.carel_encoder_forward(C.byref(ea), st), "carel_encoder_forward")
-        x_last_ptr = lib.carel_encoder_x_last(C.byref(ea))
-        if c.cls is not None:
-            cls_rows, n_rows = c.cls.compact, c.cls.n_cls
-        else:
-            cls_rows, n_rows = (None, c.Bp * c.S) if c.pack is None else (c.pack.cu, c.pack.n_tokens)
         ta = self._en_tail_args(c, x_last_ptr, cls_rows, n_rows, train_drop)
         L.check(lib.carel_en_tail_latents(C.byref(ta), st), "carel_en_tail_latents")
         if self.bow_loss:
             ops.en_tail_losses_bow(ta, ops.en_bow_args(c.buf.bow_work))
         else:
             L.check(lib.carel_en_tail_losses(C.byref(ta), st), "carel_en_tail_losses")
-        c.ea, c.ta, c.ws = ea, ta, ws
+        c.ta = ta
         c.keep = (cls_rows,)
 
     def _group_has_grad(self, g):
@@ -411,20 +395,17 @@ class DrlClassifier(_Base):
                 share(group, 2, go, acc)
                 touched[group] = True
             lo, hi = self._group_ranges["vae"]
-            accumulate = self._group_has_grad("vae")
-            prev = self._flat_grad[lo:hi].clone() if accumulate else None
-            ea = c.ea
-            ea.dx = c.buf.dx_last.data_ptr()
-            L.check(lib.carel_en_tail_backward(C.byref(c.ta), go.data_ptr(), st), "carel_en_tail_backward")
-            h_lo = self._offs[OTHER_HEADS[0] + ".weight"]          # classifier / decoder gradients were produced for grad_output = 1
-            ops.scale_(self._flat_grad[h_lo:hi], go)
-            if self._dp is not None:          # pooler, heads and (now complete) discriminator gradients: one bucket.  Under data
-                self._dp.tail_done()          # parallelism the discriminator backward calls must precede this one (the reference's order)
-            self._backward_encoder(ea, accumulate)
-            if self._dp is not None:
-                self._dp.backward_done()
-            if accumulate:
-                self._flat_grad[lo:hi].add_(prev)
+            with self._overwriting_grads(self._group_has_grad("vae"), lo, hi) as accumulate:
+                ea = c.ea
+                ea.dx = c.buf.dx_last.data_ptr()
+                L.check(lib.carel_en_tail_backward(C.byref(c.ta), go.data_ptr(), st), "carel_en_tail_backward")
+                h_lo = self._offs[OTHER_HEADS[0] + ".weight"]          # classifier / decoder gradients were produced for grad_output = 1
+                ops.scale_(self._flat_grad[h_lo:hi], go)
+                if self._dp is not None:          # pooler, heads and (now complete) discriminator gradients: one bucket.  Under data
+                    self._dp.tail_done()          # parallelism the discriminator backward calls must precede this one (the reference's order)
+                self._backward_encoder(ea, accumulate)
+                if self._dp is not None:
+                    self._dp.backward_done()
             touched["vae"] = True
         for g in touched:
             self._bind_group(g)
@@ -473,34 +454,20 @@ class DrlClassifier(_Base):
             self._noise = None
         else:
             eps_e, eps_c = torch.randn(o.ec_dim, device=dev), torch.randn(o.ec_dim, device=dev)     # emotion first (:347-348)
-        N, S0 = input_ids.shape
+        N = input_ids.shape[0]
         out = torch.empty(N, device=dev, dtype=torch.float32)
         self._refresh_shadow()
         lib = L.load()
         LW = 2 * o.con_dim + 4 * o.ec_dim
+        null = SimpleNamespace(data_ptr=lambda: None)
         for s in range(0, N, chunk):
-            ids = input_ids[s:s + chunk]
-            B = ids.shape[0]
-            Bp, S = self._padded_shape(B, S0)
-            c = _Call()
-            c.B, c.S, c.Bp, c.labels, c.seed = B, S, Bp, None, 0
-            ids, att = self._prep_ids(ids, Bp, S, self.cfg.pad_id), self._prep_ids(att_masks[s:s + chunk], Bp, S)
-            tt = None if token_type_ids is None else self._prep_ids(token_type_ids[s:s + chunk], Bp, S)
-            ws = self._workspace(Bp, S, inference=True)
-            pack = self._pack_info(att, B, Bp, S)
-            cls = self._cls_info(B, Bp, S, pack, dev)
-            ea = self._encoder_args(ids, att, tt, ws, Bp, S, True, False, 0, 0, pack, cls)
-            L.check(lib.carel_encoder_forward(C.byref(ea), L.current_stream()), "carel_encoder_forward")
-            key = ("en_lat", B)
-            buf = self._ws.get(key)
-            if buf is None:       # latents only: the loss-side buffers of carel_en_tail_args stay NULL
-                null = SimpleNamespace(data_ptr=lambda: None)
-                buf = SimpleNamespace(pooled=torch.empty(B, H, device=dev), lat=torch.empty(B, LW, device=dev), z=null, terms=null, work=null,
-                                      dx_last=null)
-                self._ws[key] = buf
-            c.buf = buf
-            cls_rows = cls.compact if cls is not None else (None if pack is None else pack.cu)
-            ta = self._en_tail_args(c, lib.carel_encoder_x_last(C.byref(ea)), cls_rows, 0, False)
+            c = self._prepare_inputs(input_ids[s:s + chunk], att_masks[s:s + chunk], None if token_type_ids is None else token_type_ids[s:s + chunk])
+            B, c.labels, c.seed = c.B, None, 0
+            x_last_ptr, cls_rows, _ = self._run_encoder(c, False, False, 0, 0, weights_ready=True)
+            # latents only: the loss-side buffers of carel_en_tail_args stay NULL
+            c.buf = buf = self._cached(("en_lat", B), lambda: SimpleNamespace(
+                pooled=torch.empty(B, H, device=dev), lat=torch.empty(B, LW, device=dev), z=null, terms=null, work=null, dx_last=null))
+            ta = self._en_tail_args(c, x_last_ptr, cls_rows, 0, False)
             L.check(lib.carel_en_tail_latents(C.byref(ta), L.current_stream()), "carel_en_tail_latents")
             L.check(lib.carel_en_pair_logits(buf.lat.data_ptr(), LW, 2 * o.con_dim, 2 * o.con_dim + 2 * o.ec_dim, eps_e.data_ptr(), eps_c.data_ptr(),
                                              self._w("pair_classifier.weight"), self._w("pair_classifier.bias"), B, o.ec_dim,

@@ -358,19 +358,16 @@ class SentenceTransformer(nn.Module):
         ids = features["input_ids"].to(dev)
         att = features.get("attention_mask", features.get("attention_masks")).to(dev)
         tt = features.get("token_type_ids")
-        B, S = ids.shape
-        Bp, S = m._padded_shape(B, S)
-        c = SimpleNamespace(B=B, S=S, Bp=Bp)
-        c.ids, c.att = m._prep_ids(ids, Bp, S, m.cfg.pad_id), m._prep_ids(att, Bp, S)
-        c.tt = None if tt is None else m._prep_ids(tt.to(dev), Bp, S)
         lens = features.get("seq_lengths")
         if lens is None:
             lens = att.sum(1).tolist()                        # host list (one read-back; loaders that know the lengths pass them)
-        c.lens = [int(v) for v in lens]
-        c.pack = m._pack_info(c.att, B, Bp, S, c.lens)
+        lens = [int(v) for v in lens]
+        c = m._prepare_inputs(ids, att, None if tt is None else tt.to(dev), lens)
+        c.lens = lens
+        B, S = c.B, c.S
         self._fwd += 1
         c.seed = (m.dropout_base_seed * 1000003 + 7919 * self._fwd) & 0xFFFFFFFF
-        rows = c.pack.n_tokens if c.pack is not None else Bp * S
+        rows = c.pack.n_tokens if c.pack is not None else c.Bp * S
         c.rows = rows
         if c.pack is not None:
             row0 = c.pack.cu[:B]
@@ -392,18 +389,11 @@ class SentenceTransformer(nn.Module):
 
     def _forward(self, c, training):
         m = self._m
-        if m._adam_hook is not None:
-            m._adam_hook._join()
-        m._refresh_shadow()
-        ws = m._workspace(c.Bp, c.S, inference=not training)
-        ea = m._encoder_args(c.ids, c.att, c.tt, ws, c.Bp, c.S, not training, m.training, c.seed, 0, c.pack, None)
+        x_last, _, _ = m._run_encoder(c, training, m.training, c.seed, 0, want_cls=False)      # mean pooling reads every attended token
         lib = L.load()
-        L.check(lib.carel_encoder_forward(C.byref(ea), L.current_stream()), "carel_encoder_forward")
-        x_last = lib.carel_encoder_x_last(C.byref(ea))
         emb = torch.empty((c.B, H), device=m._flat.device, dtype=torch.float32)
         L.check(lib.carel_mean_pool_fwd(x_last, c.row0.data_ptr(), c.len_dev.data_ptr(), c.B, H, emb.data_ptr(), L.current_stream()), "carel_mean_pool_fwd")
-        c.ea, c.ws = ea, ws
-        if self.normalize:                                   # models.Normalize
+        if self.normalize:                                  # models.Normalize
             c.y, c.norm = torch.empty_like(emb), torch.empty(c.B, device=emb.device, dtype=torch.float32)
             L.check(lib.carel_l2_normalize_fwd(emb.data_ptr(), c.B, H, c.y.data_ptr(), c.norm.data_ptr(), L.current_stream()), "carel_l2_normalize_fwd")
             return c.y
@@ -412,25 +402,18 @@ class SentenceTransformer(nn.Module):
     def _backward(self, c, g):
         m = self._m
         lib = L.load()
-        first = m._named[m._order[0]]
-        accumulate = first.grad is not None
-        prev = m._flat_grad.clone() if accumulate else None
-        key = ("st_dx", c.rows)
-        dx = m._ws.get(key)
-        if dx is None:
-            dx = m._ws[key] = torch.empty((c.rows, H), device=g.device, dtype=torch.float32)
-        if self.normalize:
-            gp = torch.empty_like(g)
-            L.check(lib.carel_l2_normalize_bwd(g.data_ptr(), c.y.data_ptr(), c.norm.data_ptr(), c.B, H, gp.data_ptr(), L.current_stream()), "carel_l2_normalize_bwd")
-            g = gp
-        L.check(lib.carel_mean_pool_bwd(g.data_ptr(), c.row_sample.data_ptr(), c.len_dev.data_ptr(), c.rows, H, dx.data_ptr(), L.current_stream()),
-                "carel_mean_pool_bwd")
-        c.ea.dx = dx.data_ptr()
-        m._backward_encoder(c.ea, accumulate)
-        if self.mpnet:                                       # no token types in MPNet: the placeholder row takes no gradient (and so never moves)
-            m._grad_view(TT_KEY).zero_()
-        if accumulate:
-            m._flat_grad.add_(prev)
+        with m._overwriting_grads(m._group_has_grad("vae")) as accumulate:      # "vae": the engine's optimised prefix, the encoder first
+            dx = m._cached(("st_dx", c.rows), lambda: torch.empty((c.rows, H), device=g.device, dtype=torch.float32))
+            if self.normalize:
+                gp = torch.empty_like(g)
+                L.check(lib.carel_l2_normalize_bwd(g.data_ptr(), c.y.data_ptr(), c.norm.data_ptr(), c.B, H, gp.data_ptr(), L.current_stream()), "carel_l2_normalize_bwd")
+                g = gp
+            L.check(lib.carel_mean_pool_bwd(g.data_ptr(), c.row_sample.data_ptr(), c.len_dev.data_ptr(), c.rows, H, dx.data_ptr(), L.current_stream()),
+                    "carel_mean_pool_bwd")
+            c.ea.dx = dx.data_ptr()
+            m._backward_encoder(c.ea, accumulate)
+            if self.mpnet:                                   # no token types in MPNet: the placeholder row takes no gradient (and so never moves)
+                m._grad_view(TT_KEY).zero_()
         m._bind_grads()
 
     def forward(self, features):
@@ -578,12 +561,7 @@ class FusedAdamW(M.FusedAdam):
         m = self.model
         lib = L.load()
         lo, hi = self._lo, self._hi
-        a = L.AdamArgs()
-        a.param, a.grad = m._flat.data_ptr() + 4 * lo, m._flat_grad.data_ptr() + 4 * lo
-        a.exp_avg, a.exp_avg_sq = self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr()
-        a.shadow_bf16 = m._shadow.data_ptr() + 2 * lo
-        a.n, a.step = hi - lo, self.step_count + 1
-        a.lr, a.beta1, a.beta2, a.eps = self.param_groups[0]["lr"], self.betas[0], self.betas[1], self.eps
+        a = self._adam_args(lo, hi)
         a.grad_scale = 1.0
         if self.max_grad_norm is not None:
             L.check(lib.carel_grad_norm_clip(a.grad, hi - lo, self.max_grad_norm, self._norm_scratch.data_ptr(), self._norm_out.data_ptr(),
