@@ -50,6 +50,17 @@ class PdistArgs(C.Structure):
                 ("dist_out", C.c_void_p), ("grad_dist", C.c_void_p), ("g1", C.c_void_p), ("g2", C.c_void_p)]
 
 
+class MmdPermArgs(C.Structure):
+    """carel_mmd_perm_args (include/carel_hip.h)."""
+    _fields_ = [("matrix", C.c_void_p), ("ldm", C.c_int64), ("labels", C.c_void_p),
+                ("n1", C.c_int32), ("n2", C.c_int32), ("n_permutations", C.c_int32),
+                ("a00", C.c_double), ("a01", C.c_double), ("a11", C.c_double),
+                ("stats", C.c_void_p), ("count", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+PERM_MAX_N, PERM_MAX_PERMUTATIONS = 8192, 65535
+
+
 class EmbedArgs(C.Structure):
     _fields_ = [("input_ids", C.c_void_p), ("token_type_ids", C.c_void_p),
                 ("word_emb", C.c_void_p), ("pos_emb", C.c_void_p), ("type_emb", C.c_void_p),
@@ -264,6 +275,10 @@ SIGNATURES = {
     "carel_l2_normalize_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "carel_rbf_mmd_fwd": (C.c_int, [C.POINTER(MmdArgs), C.c_void_p]),
     "carel_rbf_mmd_bwd": (C.c_int, [C.POINTER(MmdArgs), C.c_void_p]),
+    "carel_rbf_gram": (C.c_int, [C.POINTER(MmdArgs), C.c_void_p]),
+    "carel_mmd_perm_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "carel_mmd_perm_test": (C.c_int, [C.POINTER(MmdPermArgs), C.c_void_p]),
+    "carel_sample_latents": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "carel_pdist_fwd": (C.c_int, [C.POINTER(PdistArgs), C.c_void_p]),
     "carel_pdist_bwd": (C.c_int, [C.POINTER(PdistArgs), C.c_void_p]),
     "carel_hsic_fwd": (C.c_int, [C.POINTER(HsicArgs), C.c_void_p]),

@@ -395,12 +395,83 @@ class MMDStatistic:
         ops._chk_cuda(sample_1, sample_2)
         return _MMDFn.apply(sample_1, sample_2, [float(a) for a in alphas], bool(ret_matrix))
 
-    def pval(self, distances, n_permutations=1000):   # dead in the reference too (:571-577 calls a stub)
-        return permutation_test_mat(distances, self.n_1, self.n_2, n_permutations, a00=self.a00, a11=self.a11, a01=self.a01)
+    def pval(self, distances, n_permutations=1000, *, labels=None, generator=None, return_stats=False):
+        """The reference's `pval` (:571-577) on the matrix that `__call__(..., ret_matrix=True)` or `ops.rbf_gram` returns: the
+        permutation p-value of the statistic, a Python float (`permutation_test_mat`; the reference calls a stub there)."""
+        return permutation_test_mat(distances, self.n_1, self.n_2, n_permutations, a00=self.a00, a11=self.a11, a01=self.a01,
+                                    labels=labels, generator=generator, return_stats=return_stats)
 
 
-def permutation_test_mat(*args, **kwargs):  # the reference's stub (:599-600)
-    pass
+def random_labellings(n_1, n_2, n_permutations, device, generator=None):
+    """uint8 [n_permutations + 1, n_1 + n_2] on `device`: the observed labelling [0] * n_1 + [1] * n_2 first, then uniformly random
+    labellings with n_2 ones each -- the first n_2 places of a stable argsort of uniform draws, so a seeded generator repeats them
+    (the draws are made on the generator's own device)."""
+    n, P = n_1 + n_2, int(n_permutations)
+    labels = torch.zeros((P + 1, n), dtype=torch.uint8, device=device)
+    labels[0, n_1:] = 1
+    u = torch.rand((P, n), generator=generator, device=device if generator is None else generator.device)
+    labels[1:].scatter_(1, torch.argsort(u, dim=1, stable=True)[:, :n_2].to(device), 1)
+    return labels
+
+
+def permutation_test_mat(matrix, n_1, n_2, n_permutations, a00=1, a01=0, a11=1, *, labels=None, generator=None, return_stats=False):
+    """The reference's stub (:599-600) filled in; THE DEFINITION IS THIS PROJECT'S OWN (include/carel_hip.h, carel_mmd_perm_test).
+    stat(g) = sum over i != j of c(g_i, g_j) matrix[i, j] with c(0,0) = a00, c(1,1) = a11, c(0,1) = c(1,0) = a01; the p-value is the
+    share of the n_permutations relabellings whose statistic is >= the observed one's (labelling [0] * n_1 + [1] * n_2, not itself
+    among them).  matrix: [n, n] CUDA tensor, CPU tensor or ndarray (it goes to the device as float32).  labels: uint8
+    [n_permutations, n] relabellings with n_2 ones each (default: `random_labellings` from `generator`).  Returns a Python float, with
+    return_stats (pval, stats float64 [n_permutations + 1] on the device, count)."""
+    if not torch.cuda.is_available():
+        raise L.CarelError("permutation_test_mat runs on the GPU (carel_mmd_perm_test); there is no CPU fallback.")
+    m = torch.as_tensor(matrix).detach()
+    dev = m.device if m.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    m = m.to(dev, torch.float32)
+    n_1, n_2, P = int(n_1), int(n_2), int(n_permutations)
+    n = n_1 + n_2
+    if n_1 < 2 or n_2 < 2 or n > L.PERM_MAX_N or not 1 <= P <= L.PERM_MAX_PERMUTATIONS:
+        raise L.CarelError("permutation_test_mat: n_1, n_2 >= 2, n_1 + n_2 <= %d and 1 <= n_permutations <= %d are required"
+                           % (L.PERM_MAX_N, L.PERM_MAX_PERMUTATIONS))
+    if m.dim() != 2 or tuple(m.shape) != (n, n):
+        raise L.CarelError("permutation_test_mat: the matrix must be [n_1 + n_2, n_1 + n_2]")
+    if m.stride(1) != 1:
+        m = m.contiguous()
+    with torch.cuda.device(dev):
+        if labels is None:
+            full = random_labellings(n_1, n_2, P, dev, generator)
+        else:
+            lab = torch.as_tensor(labels)
+            if lab.dtype != torch.uint8 or tuple(lab.shape) != (P, n):
+                raise L.CarelError("permutation_test_mat: labels must be uint8 [n_permutations, n_1 + n_2]")
+            lab = lab.to(dev)
+            if bool((lab > 1).any()) or bool((lab.sum(dim=1, dtype=torch.int64) != n_2).any()):
+                raise L.CarelError("permutation_test_mat: every row of labels must hold exactly n_2 ones and zeros otherwise")
+            full = torch.cat((random_labellings(n_1, n_2, 0, dev)[:1], lab), 0)
+        stats, count = ops.mmd_perm_test(m, full, n_1, n_2, a00, a01, a11)
+        c = int(count.item())
+    pval = c / P
+    return (pval, stats, c) if return_stats else pval
+
+
+def mmd_two_sample_test(sample_1, sample_2, alphas, n_permutations=1000, eps=1e-5, labels=None, generator=None, return_stats=False):
+    """The two-sample test from the samples: the tiled Gram matrix (carel_rbf_gram, n_1 + n_2 <= 8192), then `permutation_test_mat`
+    with MMDStatistic's coefficients.  Returns (mmd, pval) as Python floats -- mmd is the observed statistic, what
+    MMDStatistic.__call__ computes -- and with return_stats (mmd, pval, stats, count)."""
+    if not torch.cuda.is_available():
+        raise L.CarelError("mmd_two_sample_test runs on the GPU (carel_rbf_gram, carel_mmd_perm_test); there is no CPU fallback.")
+    s1, s2 = torch.as_tensor(sample_1).detach(), torch.as_tensor(sample_2).detach()
+    dev = s1.device if s1.is_cuda else (s2.device if s2.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    s1, s2 = s1.to(dev, torch.float32), s2.to(dev, torch.float32)
+    if s1.dim() != 2 or s2.dim() != 2:
+        raise L.CarelError("mmd_two_sample_test: two [n, d] samples are required")
+    s1, s2 = (s if s.stride(1) == 1 else s.contiguous() for s in (s1, s2))
+    if s1.shape[0] < 2 or s2.shape[0] < 2:
+        raise L.CarelError("mmd_two_sample_test: both samples need at least 2 rows")
+    stat = MMDStatistic(s1.shape[0], s2.shape[0])
+    with torch.cuda.device(dev):
+        kern = ops.rbf_gram(s1, s2, [float(a) for a in alphas], eps)
+    pval, stats, count = stat.pval(kern, n_permutations, labels=labels, generator=generator, return_stats=True)
+    mmd = float(stats[0])
+    return (mmd, pval, stats, count) if return_stats else (mmd, pval)
 
 
 class _PdistFn(torch.autograd.Function):
@@ -1375,6 +1446,18 @@ class DrlClassifier(nn.Module):
         W, _ = self._tail_weights()
         prob, _ = ops.pair_probs_draws(lat, eps_e, eps_c, W["pair_classifier.weight"], W["pair_classifier.bias"], self.opt.ec_dim)
         return (prob, (eps_e, eps_c)) if return_noise else prob
+
+    def latent_two_sample_test(self, lat, n_permutations=1000, noise=None, alphas=None, labels=None, generator=None, return_stats=False):
+        """Are the emotion and the cause latents distinguishable (extension)?  The permutation two-sample test of `mmd_two_sample_test`
+        on z_e, z_c [N, ec_dim] sampled from the latents of `pair_latents` the way draw 0 of `pair_probabilities_from` samples them
+        (noise = (eps_e, eps_c) replays a chosen draw; without it one is drawn like a forward call's).  alphas defaults to the kernel
+        width of the model's own MMD loss term.  2 N <= 8192.  Returns (mmd, pval), with return_stats (mmd, pval, stats, count)."""
+        self._require_cuda()
+        D = self.opt.ec_dim
+        eps_e, eps_c = self._draws_noise(lat.device, 1, noise)
+        z = ops.sample_latents(lat, eps_e[0].contiguous(), eps_c[0].contiguous(), D)
+        return mmd_two_sample_test(z[:, :D], z[:, D:], ops.MODEL_MMD_ALPHAS if alphas is None else alphas, n_permutations, eps=1e-5,
+                                   labels=labels, generator=generator, return_stats=return_stats)
 
     def draw_counts(self, lat, labels, n_draws, groups=None, noise=None, return_noise=False, n_groups=None):
         """int64 [K, G, 3]: TP / FP / FN of `prob > 0.5` (numpy's .round() of a probability, ref :282: exactly 0.5 predicts 0) against

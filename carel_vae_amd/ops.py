@@ -110,6 +110,59 @@ def _mmd_args(s1, s2, alphas, eps):
     return a
 
 
+MODEL_MMD_ALPHAS = (0.1,)          # the kernel width of the training loss's MMD term (tail_args: mmd_alpha)
+
+
+def rbf_gram(s1, s2, alphas, eps=1e-5):
+    """carel_rbf_gram: the [n1 + n2, n1 + n2] kernel matrix of two samples, tiled (n1 + n2 <= 8192), bitwise symmetric."""
+    _chk_cuda(s1, s2)
+    a = _mmd_args(s1, s2, alphas, eps)
+    n = s1.shape[0] + s2.shape[0]
+    kern = torch.empty((n, n), device=s1.device, dtype=torch.float32)
+    a.kernels_out = kern.data_ptr()
+    L.check(L.load().carel_rbf_gram(C.byref(a), L.current_stream()), "carel_rbf_gram")
+    return kern
+
+
+def mmd_perm_test(matrix, labels, n1, n2, a00, a01, a11):
+    """carel_mmd_perm_test: matrix f32 [n, n] (rows contiguous), labels uint8 [P+1, n] whose row 0 is the observed labelling.
+    Returns (stats f64 [P+1], count int32 [1]) on the device; nothing is read back."""
+    _chk_cuda(matrix, labels)
+    n = int(n1) + int(n2)
+    if matrix.dtype != torch.float32 or matrix.dim() != 2 or tuple(matrix.shape) != (n, n) or matrix.stride(1) != 1:
+        raise L.CarelError("mmd_perm_test: the matrix must be float32 [n1 + n2, n1 + n2] with contiguous rows")
+    if labels.dtype != torch.uint8 or labels.dim() != 2 or labels.shape[1] != n or labels.shape[0] < 2 or not labels.is_contiguous():
+        raise L.CarelError("mmd_perm_test: labels must be contiguous uint8 [n_permutations + 1, n1 + n2]")
+    if labels.device != matrix.device:
+        raise L.CarelError("mmd_perm_test: the matrix and the labels are on different devices")
+    P = labels.shape[0] - 1
+    lib = L.load()
+    a = L.MmdPermArgs()
+    a.matrix, a.ldm, a.labels = matrix.data_ptr(), matrix.stride(0), labels.data_ptr()
+    a.n1, a.n2, a.n_permutations = int(n1), int(n2), P
+    a.a00, a.a01, a.a11 = float(a00), float(a01), float(a11)
+    stats = torch.empty(P + 1, device=matrix.device, dtype=torch.float64)
+    count = torch.empty(1, device=matrix.device, dtype=torch.int32)
+    nbytes = int(lib.carel_mmd_perm_workspace_bytes(n, P))
+    work = torch.empty(max(nbytes, 8) // 8, device=matrix.device, dtype=torch.float64)
+    a.stats, a.count, a.workspace, a.workspace_bytes = stats.data_ptr(), count.data_ptr(), work.data_ptr(), nbytes
+    L.check(lib.carel_mmd_perm_test(C.byref(a), L.current_stream()), "carel_mmd_perm_test")
+    return stats, count
+
+
+def sample_latents(lat, eps_e, eps_c, D):
+    """carel_sample_latents: z f32 [N, 2 D] = [mu_e + eps_e e^lv_e | mu_c + eps_c e^lv_c] of lat f32 [N, 4 D] with one noise pair [D]."""
+    _chk_cuda(lat, eps_e, eps_c)
+    if lat.dtype != torch.float32 or lat.dim() != 2 or lat.shape[1] != 4 * D or not lat.is_contiguous() or lat.shape[0] < 1:
+        raise L.CarelError("sample_latents: lat must be contiguous float32 [N, 4 * ec_dim]")
+    if any(e.dtype != torch.float32 or e.numel() != D or not e.is_contiguous() for e in (eps_e, eps_c)):
+        raise L.CarelError("sample_latents: eps_e and eps_c must be contiguous float32 [ec_dim]")
+    z = torch.empty((lat.shape[0], 2 * D), device=lat.device, dtype=torch.float32)
+    L.check(L.load().carel_sample_latents(lat.data_ptr(), eps_e.data_ptr(), eps_c.data_ptr(), lat.shape[0], D, z.data_ptr(), L.current_stream()),
+            "carel_sample_latents")
+    return z
+
+
 def kl_anneal_weight(iteration, opt):
     """ref :515-523 (host double arithmetic) gated by :242/:248."""
     if iteration < opt.kl_ann_iterations:

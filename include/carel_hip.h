@@ -746,6 +746,50 @@ typedef struct carel_mmd_args {
 int carel_rbf_mmd_fwd(const carel_mmd_args* args, void* stream);
 int carel_rbf_mmd_bwd(const carel_mmd_args* args, void* stream);
 
+/* The kernel matrix alone, tiled: kernels_out f32 [(n1+n2)^2] of the same struct (mmd_out and the backward fields are not read), each
+ * element by the expression carel_rbf_mmd_fwd evaluates, sum_a expf(-alpha_a * (eps + |d2|)), so the matrix is bitwise symmetric.
+ * Any n1, n2 >= 1 with n1 + n2 <= 8192 (carel_rbf_mmd_fwd keeps both samples in one workgroup's LDS and stops near 1 600 rows at d = 24;
+ * this one holds 128 rows per workgroup whatever n is), d in 1..64, 1..8 alphas, row strides >= d.  One launch.  Errors before it:
+ * a NULL struct / sample / kernels_out, n_alphas outside 1..8, a row stride below d -> CAREL_ERR_ARG; the shape -> CAREL_ERR_SHAPE. */
+int carel_rbf_gram(const carel_mmd_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Permutation two-sample test on a kernel matrix: the body of MMDStatistic.pval / permutation_test_mat.  The reference's function
+ * is a stub (ref :599-600) and the package it came from is not at hand, so this DEFINITION IS THE PROJECT'S OWN (parity unpinned):
+ *   M f32 [n, n], n = n1 + n2, not necessarily symmetric, diagonal never read as a value (a NaN there changes nothing);
+ *   for a labelling g in {0,1}^n:  stat(g) = sum over i != j of c(g_i, g_j) M_ij,  c(0,0) = a00, c(1,1) = a11, c(0,1) = c(1,0) = a01;
+ *   labels u8 [P+1, n] contiguous, row 0 = the observed labelling [0]*n1 + [1]*n2 (with MMDStatistic's coefficients stat(row 0) is
+ *   what __call__ returns), rows 1..P the relabellings -- any 0 / non-zero bytes: the CALLER sees to it that each row holds n2 ones;
+ *   stats f64 [P+1] = stat of every row;  count i32 [1] = #{p in 1..P : stats[p] >= stats[0]}, compared on the doubles on the device;
+ *   p-value = count / P (the observed labelling is not among the P).
+ * The f32 arithmetic is a chain of at most 32 additions per partial sum; everything after it is double, in an order fixed by indices:
+ * equal rows of `labels` give equal bits wherever they stand, and so do two runs (csrc/mmd_perm.hip; the bound: tests/perm_restate.py).
+ * workspace: carel_mmd_perm_workspace_bytes(n, P) bytes of device memory (8-byte aligned), fully rewritten by every call; the
+ * function is pure host code and returns 0 for a shape outside the limits.
+ * Limits: n1, n2 >= 2, n <= 8192, 1 <= P <= 65535, ldm >= n.  Four launches on `stream`, no allocation, no host synchronisation.
+ * Errors before the first launch: a NULL struct / matrix / labels / stats / count / workspace, ldm < n, a workspace smaller than
+ * stated -> CAREL_ERR_ARG; n1, n2, n or P outside the limits -> CAREL_ERR_SHAPE.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct carel_mmd_perm_args {
+  const void* matrix;       /* f32 [n, n], row stride ldm */
+  int64_t ldm;
+  const void* labels;       /* u8 [P+1, n] */
+  int32_t n1, n2;
+  int32_t n_permutations;   /* P */
+  double a00, a01, a11;
+  void* stats;              /* f64 [P+1] */
+  void* count;              /* i32 [1] */
+  void* workspace;
+  int64_t workspace_bytes;
+} carel_mmd_perm_args;
+int64_t carel_mmd_perm_workspace_bytes(int32_t n, int32_t n_permutations);
+int carel_mmd_perm_test(const carel_mmd_perm_args* args, void* stream);
+
+/* z f32 [n, 2*ec_dim] = [mu_e + eps_e * exp(lv_e) | mu_c + eps_c * exp(lv_c)] of every row of lat f32 [n, 4*ec_dim] (the output of
+ * carel_tail_latents) with ONE noise pair eps_e, eps_c f32 [ec_dim]: the samples that carel_pair_probs / draw 0 of
+ * carel_pair_probs_draws feed to the pair head, written out (the two-sample test on a model's latents).  ec_dim in 1..32, n >= 1. */
+int carel_sample_latents(const void* lat, const void* eps_e, const void* eps_c, int32_t n, int32_t ec_dim, void* z, void* stream);
+
 /* Replaces `pdist(sample_1, sample_2, norm=2, eps)` (ref :580-589, the live L2 branch) and its autograd backward:
  * dist[i][j] = sqrt(eps + |  |s1_i|^2 + |s2_j|^2 - 2 s1_i . s2_j  |), computed from the squared distance itself (no
  * exp / log round trip), so far-apart samples (d2 >> 100) and near-coincident ones are both exact to fp32 rounding. */
