@@ -1156,8 +1156,9 @@ extern "C" int carel_tail_losses_tiled(const carel_tail_args* a, void* stream_) 
 
 // Back-propagate d(loss)/d lat through the latent heads and the pooler into the encoder output.
 // grad_out_dev (device f32 scalar, or NULL for 1.0) is the upstream gradient of the loss: it scales dlat
-// here; the classifier / decoder gradients written by carel_tail_losses are scaled by the caller with
-// carel_scale_f32 (they are linear in it).
+// in carel_tail_backward_dz; the classifier / decoder gradients written by carel_tail_losses are the caller's to
+// scale (they are linear in it): the Python models add grad_output x them into .grad with carel_axpy_f32.
+// carel_scale_f32 is the in-place form, kept as a tested utility of the C ABI (tests/test_gpu_tail_sweep.py).
 extern "C" int carel_scale_f32(void* x, int64_t n, const void* scale_dev, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !scale_dev || n <= 0) return set_error(CAREL_ERR_ARG, "carel_scale_f32: bad arguments");

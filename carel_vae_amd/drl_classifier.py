@@ -259,7 +259,8 @@ def _init_like_reference(model, gen=None):
 # ----------------------------------------------------------------------------------------------
 class _TrainLoss(torch.autograd.Function):
     """Whole-step forward; `anchor` is a dummy requires-grad tensor that makes autograd call backward.
-    Gradients are written by the kernels straight into model._flat_grad (aliased by every .grad)."""
+    Gradients are written by the backward kernels straight into model._flat_grad (aliased by every .grad); the classifier / decoder
+    gradients, which the forward's loss kernels produce, wait in model._head_img until backward adds them in (_flatten)."""
 
     @staticmethod
     def forward(ctx, anchor, model, call):
@@ -670,6 +671,11 @@ class DrlClassifier(nn.Module):
         self._enc_ws = {}
         self._pair_lo = offs[self._pair_range_names[0]]
         self._pair_hi = offs[self._pair_range_names[1]] + named[self._pair_range_names[1]].numel()
+        # the classifier / decoder gradients come out of the FORWARD's loss kernels (for grad_output = 1).  They are written to an image of
+        # their range beside the gradient buffer, so that a forward leaves every .grad alone; the backward adds grad_output x the image
+        # into the range (or overwrites it), like the adversaries' images of the gan model
+        self._head_range = self._head_grad_range()
+        self._head_img = torch.zeros(self._head_range[1] - self._head_range[0], device=dev) if dev.type == "cuda" else None
         if getattr(self, "_gan", False):
             end = lambda k: offs[k] + ((named[k].numel() + 63) & ~63)        # noqa: E731
             self._group_ranges = {"vae": (0, self._n_opt)}
@@ -678,6 +684,18 @@ class DrlClassifier(nn.Module):
             self._disc_lo, self._disc_hi = self._group_ranges[GAN_DISCS[0]][0], self._group_ranges[GAN_DISCS[-1]][1]
             # gradient images of the discriminator range for unit upstream gradients: [0] own loss, [1] entropy term (carel_gan_disc)
             self._disc_img = [torch.zeros(self._disc_hi - self._disc_lo, device=dev) for _ in range(2)] if dev.type == "cuda" else None
+
+    def _head_grad_range(self):
+        """[lo, hi) of the flat buffer that holds the gradients the loss kernels produce: decoder .. pair classifier."""
+        return self._offs["decoder.weight"], self._pair_hi
+
+    def _head_img_view(self, k):
+        p = self._named[k]
+        o = self._offs[k] - self._head_range[0]
+        return self._head_img[o:o + p.numel()].view(p.shape)
+
+    def _g_head(self, key):
+        return self._head_img.data_ptr() + (self._offs[key] - self._head_range[0]) * 4
 
     def _apply(self, fn, *a, **kw):
         r = super()._apply(fn, *a, **kw)
@@ -1042,16 +1060,16 @@ class DrlClassifier(nn.Module):
                                                                         c.ids.device, rows=c.Bp * c.S))
 
     @contextlib.contextmanager
-    def _overwriting_grads(self, accumulate, lo=0, hi=None, keep=None):
+    def _overwriting_grads(self, accumulate, lo=0, hi=None, keep=()):
         """Around a backward that overwrites [lo, hi) of the flat gradient buffer (default: all of it).  accumulate: the caller's answer
         to "do these parameters already hold a gradient?"; then what the range held is set aside and added back afterwards, as
-        autograd accumulates.  keep = (klo, khi): a sub-range the backward leaves alone, which must not be added to itself.  Yields
-        accumulate; the caller binds the .grad views when the block is done."""
+        autograd accumulates.  keep: (klo, khi) sub-ranges that the backward leaves alone or accumulates into by itself, which must not
+        be added to themselves.  Yields accumulate; the caller binds the .grad views when the block is done."""
         prev = None
         if accumulate:
             prev = self._flat_grad[lo:hi].clone()
-            if keep is not None:
-                prev[keep[0] - lo:keep[1] - lo].zero_()
+            for klo, khi in keep:
+                prev[klo - lo:khi - lo].zero_()
         yield accumulate
         if accumulate:
             self._flat_grad[lo:hi].add_(prev)
@@ -1123,7 +1141,9 @@ class DrlClassifier(nn.Module):
         keys = ["encoder.pooler.dense.weight", "encoder.pooler.dense.bias", "decoder.weight", "decoder.bias"]
         for n in ("emotion_mu", "emotion_log_var", "cause_mu", "cause_log_var", "emotion_classifier", "cause_classifier", "pair_classifier"):
             keys += [n + ".weight", n + ".bias"]
-        return {k: self._named[k].data for k in keys}, {k: self._grad_view(k) for k in keys}
+        lo, hi = self._head_range            # the loss kernels' outputs go to the image (_flatten), the backward's into .grad
+        return ({k: self._named[k].data for k in keys},
+                {k: self._head_img_view(k) if lo <= self._offs[k] < hi else self._grad_view(k) for k in keys})
 
     def _grad_view(self, k):
         p = self._named[k]
@@ -1251,8 +1271,13 @@ class DrlClassifier(nn.Module):
             self._run_backward(c, go, None)
 
     def _run_backward(self, c, grad_out, grad_z=None):
-        # the adversaries' range is not rewritten below: it must not be added to itself
-        keep = (self._disc_lo, self._disc_hi) if self._gan else None
+        # the adversaries' range (gan) and the approximation network's (vi: _AprxLoss.backward owns it; the tail of the flat buffer) are
+        # not rewritten below, and the classifier / decoder range accumulates by itself: they must not be added to themselves
+        keep = [self._head_range]
+        if self._gan:
+            keep.append((self._disc_lo, self._disc_hi))
+        if self._aprx_names:
+            keep.append((self._offs[self._aprx_names[0]], self._flat_grad.numel()))
         with self._overwriting_grads(self._group_has_grad("vae"), keep=keep) as accumulate:
             go = grad_out.to(torch.float32).reshape(1).contiguous()      # device scalar, never read on the host
             ea = c.ea
@@ -1263,9 +1288,9 @@ class DrlClassifier(nn.Module):
                 ops.adapter_backward(c.ad)
                 if self._adapter_train_names:        # opt.train_adapter: overwritten like every gradient of this call
                     ops.adapter_backward_weights(c.ad, ops.adapter_wgrad_args(self._ws[("adapter", c.B, c.S)], self._adapter_grads()))
-            # classifier / decoder gradients were produced for grad_output = 1: one contiguous range of the flat buffer
-            lo = self._offs["decoder.weight"]
-            ops.scale_(self._flat_grad[lo:self._pair_hi], go)
+            # classifier / decoder gradients were produced by the forward for grad_output = 1, as an image of one contiguous range
+            lo, hi = self._head_range
+            ops.axpy_(self._flat_grad[lo:hi], self._head_img, go, accumulate)
             if self._dp is not None:
                 self._dp.tail_done()
             self._backward_encoder(ea, accumulate)

@@ -210,6 +210,9 @@ class DrlClassifier(_Base):
         assert set(order) == set(named), "parameter inventory mismatch"
         return order, n_opt_names, named
 
+    def _head_grad_range(self):
+        return self._offs[OTHER_HEADS[0] + ".weight"], self._n_opt       # decoder .. content_classifier, the end of the vae group
+
     def _flatten(self):
         super()._flatten()
         offs, named = self._offs, self._named
@@ -335,11 +338,12 @@ class DrlClassifier(_Base):
         for i, h in enumerate(SMALL_DISCS):
             a.g_sdisc_w[i], a.g_sdisc_b[i] = img(0, h + ".weight"), img(0, h + ".bias")
             a.g_sdisc_ent_w[i], a.g_sdisc_ent_b[i] = img(2, h + ".weight"), img(2, h + ".bias")
-        a.d_ccls_w, a.d_ccls_b = g("content_classifier.weight"), g("content_classifier.bias")
-        a.d_emo_w, a.d_emo_b = g("emotion_classifier.weight"), g("emotion_classifier.bias")
-        a.d_cau_w, a.d_cau_b = g("cause_classifier.weight"), g("cause_classifier.bias")
-        a.d_pair_w, a.d_pair_b = g("pair_classifier.weight"), g("pair_classifier.bias")
-        a.d_dec_w, a.d_dec_b = g("decoder.weight"), g("decoder.bias")
+        gh = self._g_head                     # the loss kernels' outputs go to the image of the heads' range (_head_grad_range)
+        a.d_ccls_w, a.d_ccls_b = gh("content_classifier.weight"), gh("content_classifier.bias")
+        a.d_emo_w, a.d_emo_b = gh("emotion_classifier.weight"), gh("emotion_classifier.bias")
+        a.d_cau_w, a.d_cau_b = gh("cause_classifier.weight"), gh("cause_classifier.bias")
+        a.d_pair_w, a.d_pair_b = gh("pair_classifier.weight"), gh("pair_classifier.bias")
+        a.d_dec_w, a.d_dec_b = gh("decoder.weight"), gh("decoder.bias")
         a.d_pooler_w, a.d_pooler_b = g("encoder.pooler.dense.weight"), g("encoder.pooler.dense.bias")
         a.dx_last_f32 = b.dx_last.data_ptr()
         return a
@@ -395,12 +399,12 @@ class DrlClassifier(_Base):
                 share(group, 2, go, acc)
                 touched[group] = True
             lo, hi = self._group_ranges["vae"]
-            with self._overwriting_grads(self._group_has_grad("vae"), lo, hi) as accumulate:
+            with self._overwriting_grads(self._group_has_grad("vae"), lo, hi, keep=[self._head_range]) as accumulate:
                 ea = c.ea
                 ea.dx = c.buf.dx_last.data_ptr()
                 L.check(lib.carel_en_tail_backward(C.byref(c.ta), go.data_ptr(), st), "carel_en_tail_backward")
-                h_lo = self._offs[OTHER_HEADS[0] + ".weight"]          # classifier / decoder gradients were produced for grad_output = 1
-                ops.scale_(self._flat_grad[h_lo:hi], go)
+                # classifier / decoder gradients were produced by the forward for grad_output = 1, as an image of their range
+                ops.axpy_(self._flat_grad[self._head_range[0]:self._head_range[1]], self._head_img, go, accumulate)
                 if self._dp is not None:          # pooler, heads and (now complete) discriminator gradients: one bucket.  Under data
                     self._dp.tail_done()          # parallelism the discriminator backward calls must precede this one (the reference's order)
                 self._backward_encoder(ea, accumulate)

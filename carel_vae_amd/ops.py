@@ -464,10 +464,6 @@ def bow_expand(trip, nnz, out):
     return out
 
 
-def scale_(x, scale_dev):
-    L.check(L.load().carel_scale_f32(x.data_ptr(), x.numel(), scale_dev.data_ptr(), L.current_stream()), "carel_scale_f32")
-
-
 def pair_probs(lat, eps_e, eps_c, pair_w, pair_b, D):
     B = lat.shape[0]
     prob = torch.empty(B, device=lat.device, dtype=torch.float32)

@@ -538,7 +538,8 @@ typedef struct carel_host_pack_args {
   int64_t t_eff, t_pad;                                                           /* out */
 } carel_host_pack_args;
 int carel_host_pack_batch(carel_host_pack_args* args);
-/* x[i] *= *scale_dev  (device scalar; used to apply loss.backward()'s grad_output without a host sync) */
+/* x[i] *= *scale_dev  (device scalar: no host sync).  A utility for callers of the C ABI that scale the classifier / decoder gradients
+ * of carel_tail_losses in place; the Python models add grad_output x those gradients into .grad with carel_axpy_f32 instead. */
 int carel_scale_f32(void* x_f32, int64_t n, const void* scale_dev_f32, void* stream);
 /* offset (in floats, inside `work`) of the flag carel_tail_losses sets to 1.0 when the pair loss was
  * replaced by 0 (ref :510-511); carel_adam_step's skip_flag points at it */

@@ -41,9 +41,11 @@ def setup(B, S, V, seed, all_negative=False, ec_dim=24, e_num_class=6, disentang
     return cfg, opt, P, x_last, batch, eps_e, eps_c
 
 
-def oracle_tail(P, x_last, batch, eps_e, eps_c, opt, B, S, it, train, seed, dtype=None, **kw):
+def oracle_tail(P, x_last, batch, eps_e, eps_c, opt, B, S, it, train, seed, dtype=None, dz=None, grad_out=None, **kw):
     """-> (tail_forward's dict, pooled, {key: gradient or None}, d x_last).  dtype: the arithmetic of the oracle (weights, x_last and
-    the noise are cast to it; labels and dropout masks are exact in either)."""
+    the noise are cast to it; labels and dropout masks are exact in either).  dz [B, 2 * ec_dim] / grad_out (float): the gradients are
+    those of grad_out * loss + sum([z_e | z_c] * dz) -- an extra gradient on the sampled embeddings, which grad_out does not scale
+    (ops.tail_backward's dz_extra); without either, of the loss."""
     cast = (lambda t: t.clone()) if dtype is None else (lambda t: t.to(dtype))
     Pg = {k: cast(v).requires_grad_(True) for k, v in P.items()}
     xg = cast(x_last).requires_grad_(True)
@@ -52,13 +54,20 @@ def oracle_tail(P, x_last, batch, eps_e, eps_c, opt, B, S, it, train, seed, dtyp
     pooled = torch.tanh(xg.view(B, S, 768)[:, 0] @ Pg["encoder.pooler.dense.weight"].t() + Pg["encoder.pooler.dense.bias"])
     out = O.tail_forward(Pg, pooled, batch["emo_labels"], batch["cau_labels"], batch["labels"], batch["bow_reps"], it, opt,
                          cast(eps_e), cast(eps_c), train=train, seed=seed, **kw)
-    out["loss"].backward()
+    if dz is None and grad_out is None:
+        out["loss"].backward()
+    else:
+        obj = out["loss"] * (1.0 if grad_out is None else grad_out)
+        if dz is not None:
+            obj = obj + (torch.cat((out["z_e"], out["z_c"]), dim=1) * cast(dz)).sum()
+        obj.backward()
     return out, pooled, {k: v.grad for k, v in Pg.items()}, xg.grad
 
 
-def hip_tail(P, x_last, batch, eps_e, eps_c, opt, B, S, V, it, drop, serial=0, grad_out=None, guard=None, **kw):
+def hip_tail(P, x_last, batch, eps_e, eps_c, opt, B, S, V, it, drop, serial=0, grad_out=None, guard=None, dz_extra=None, **kw):
     """One latents -> losses -> backward run; every output (and the workspace) starts as NaN.  grad_out: float, passed to
-    carel_tail_backward as a device scalar.  guard: a torch.Generator -> the workspace (at exactly carel_tail_workspace_floats),
+    carel_tail_backward as a device scalar.  dz_extra: f32 [B, 2 * ec_dim] (any device), the extra gradient on the sampled embeddings
+    of carel_tail_backward_dz.  guard: a torch.Generator -> the workspace (at exactly carel_tail_workspace_floats),
     dx_last, z and the decoder gradients sit in tests.gpu_util.Guarded allocations, listed in buf.guards."""
     dev, nan, D = "cuda", float("nan"), opt.ec_dim
     W = {k: v.to(dev) for k, v in P.items()}
@@ -80,10 +89,11 @@ def hip_tail(P, x_last, batch, eps_e, eps_c, opt, B, S, V, it, drop, serial=0, g
     xl, ee, ec = x_last.to(dev), eps_e.to(dev), eps_c.to(dev)
     a = ops.tail_args(buf, xl, W, labels, ee, ec, opt, ops.kl_anneal_weight(it, opt), grads=G, drop=drop, **kw)
     go = None if grad_out is None else torch.tensor([grad_out], dtype=torch.float32, device=dev)
-    a._keep = (W, G, labels, xl, ee, ec, go)      # tail_args holds addresses only: the noise must outlive the calls, or go takes its block
+    dz = None if dz_extra is None else dz_extra.to(dev, torch.float32).contiguous()
+    a._keep = (W, G, labels, xl, ee, ec, go, dz)  # tail_args holds addresses only: the noise must outlive the calls, or go takes its block
     a.serial = serial
     ops.tail_latents(a)
     ops.tail_losses(a)
-    ops.tail_backward(a, go)
+    ops.tail_backward(a, go, dz)
     torch.cuda.synchronize()
     return buf, G

@@ -18,6 +18,9 @@ pytestmark = pytest.mark.gpu
 
 CFG = O.EncoderConfig(layers=2, vocab_size=900)
 DISC = ("ec_disc", "ce_disc")
+# a gradient accumulated by separate additions (or scaled after the fact) against the multiple it equals in exact arithmetic: a few fp32
+# roundings of partial sums, relative to the tensor's norm (17 x 2^-24)
+TOL_SUM_CHAIN = 1e-6
 
 
 def build(opt, wseed, cfg=CFG, train_dropout=False, disentangle="gan"):
@@ -250,7 +253,7 @@ def test_upstream_gradients_scale_each_share(golden_dir):
     dec = named["decoder.weight"].grad.clone()
     losses2 = fresh()
     losses2[2].backward()
-    assert relnorm(dec, 0.25 * named["decoder.weight"].grad) < 1e-6
+    assert relnorm(dec, 0.25 * named["decoder.weight"].grad) < TOL_SUM_CHAIN
     first = {k: named[k].grad.clone() for k in ("ec_disc.weight", "decoder.weight", "encoder.encoder.layer.0.output.dense.weight")}
     model.set_noise(eps_e, eps_c)
     model._fwd_count -= 1
@@ -258,7 +261,7 @@ def test_upstream_gradients_scale_each_share(golden_dir):
     (losses3[0] + losses3[2]).backward()
     assert torch.equal(named["ec_disc.weight"].grad, (first["ec_disc.weight"] + img[(0, "ec_disc.weight")]) + img[(1, "ec_disc.weight")])
     for k in ("decoder.weight", "encoder.encoder.layer.0.output.dense.weight"):
-        assert relnorm(named[k].grad, 2.0 * first[k]) < 1e-6, k
+        assert relnorm(named[k].grad, 2.0 * first[k]) < TOL_SUM_CHAIN, k
     # a weight other than one: to fp32 rounding of the product
     opt3 = R.gan_opt(pair_bow_dim=211, dropout=0.0, ecce_adv_loss_weight=3.0)
     model3, _ = build(opt3, wseed)

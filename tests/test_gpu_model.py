@@ -32,6 +32,9 @@ TERMS = ("mmd", "emo", "cau", "pair", "kl_e", "kl_c", "rec")
 # north_star: "ELBO matching to 1e-3 rel" -- asserted at the north-star configuration in
 # test_bench_configuration_elbo_within_1e_3_of_cpu_fp32 (measured 1.2e-4 / 1.5e-4) and, with the margin the 8-sample
 # golden needs (measured 8.9e-4), below.
+TOL_GRAD_FP32_WORST = 4e-2      # per-tensor gradient vs the fp32 oracle's autograd (test_gradients_vs_oracle): the worst tensor ...
+TOL_GRAD_FP32_MEDIAN = 1.5e-2   # ... and the median over the tensors
+TOL_FUSED_ADAM_STEP2 = 1e-6     # weights after a second Adam step, fused into backward vs plain (test_adam_fused_into_backward_equals_plain_step)
 TOL_GRAD_BF16_EMU = 5e-3        # per-tensor gradient vs the oracle that emulates the library's bf16 storage points in both directions (measured median 2e-3)
 TOL_GRAD_BF16_EMU_QK = 1.5e-2   # ... for the query / key projections (measured 0.8 .. 1.2e-2: see the test)
 TOL_TERM_BF16 = 1e-3            # mmd, emo, cau, pair, rec
@@ -227,9 +230,9 @@ def test_gradients_vs_oracle(golden_dir, name):
             assert float(got.norm()) < 0.05 * float(qb.norm()) + 1e-4, (k, float(got.norm()), float(qb.norm()))
             continue
         worst[k] = relnorm(got, g)
-    bad = {k: v for k, v in worst.items() if v > 4e-2}
+    bad = {k: v for k, v in worst.items() if v > TOL_GRAD_FP32_WORST}
     assert not bad, bad
-    assert np.median(list(worst.values())) < 1.5e-2
+    assert np.median(list(worst.values())) < TOL_GRAD_FP32_MEDIAN
     # golden slices (reference fp32): direction agreement
     for k in z.files:
         if k.startswith("g_") and float(z["gn_" + k[2:]]) > 1e-7:
@@ -527,7 +530,7 @@ def test_adam_fused_into_backward_equals_plain_step(golden_dir, name):
     for a, b in zip(res[False][0], res[True][0]):
         assert abs(a - b) <= 1e-5 * max(abs(a), 1.0), (res[False][0], res[True][0])
     for k in res[False][1][1]:
-        assert relnorm(res[True][1][1][k], res[False][1][1][k]) <= 1e-6, k
+        assert relnorm(res[True][1][1][k], res[False][1][1][k]) <= TOL_FUSED_ADAM_STEP2, k
     assert relnorm(res[True][2], res[False][2]) < 1e-4 and relnorm(res[True][3], res[False][3]) < 1e-4
 
 

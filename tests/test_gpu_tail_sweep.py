@@ -4,16 +4,18 @@ picks at run time: the batch sizes at which the decoder's sample-group count cha
 trip and at which the 160 KB LDS of the core and decoder kernels is full; every latent width path (ec_dim 24 is compiled in, every
 other width runs the run-time-width decoder, the general MMD sweep and the rowvec kernels at N != 96); 1 / 2 / 6 / 8 emotion
 logits; MMD / HSIC / no statistic; vocabularies at the 128-entry chunk edges and past 64 chunks; the dead pair head; the
-data-parallel hooks (mmd_global_kernel at both widths, partial last chunk and block); an upstream gradient.  Every case uses S = 2
+data-parallel hooks (mmd_global_kernel at both widths, partial last chunk and block); an upstream gradient; an extra gradient dz on
+the sampled embeddings (carel_tail_backward_dz's dz_extra: tail_add_dz_kernel), alone, beside a scaled loss and beside a loss scaled
+by 0, with a log-variance of 6.9 and, through the data-parallel hooks, at a batch of one; carel_scale_f32 on its own.  Every case uses S = 2
 (so the [CLS] stride matters), every output starts as NaN, the workspace / dx_last / z / decoder gradients sit between guard
 regions, and a second identical run must give the same bits.  Then the refusals of carel_tail_losses: a batch one past the LDS
 limit must be refused before anything is launched.
 
 Tolerances are those of tests/test_gpu_tail.py (test_tail_matches_oracle, test_tail_global_batch_hooks), with dx_last scaled per
 row.  Every case prints, per quantity, the worst fraction of the bound |got - ref| <= atol + rtol |ref| (1.0 = at the bound) and the
-worst |got - ref| / max|ref| (run with -s).  Worst over this module on an MI355X: NOT MEASURED YET -- the module was written without
-access to a GPU; on the CPU the fp32 oracle itself sits at <= 0.65 of the bound on pooled (3.3e-6 absolute), <= 0.10 on lat / z,
-<= 0.03 on every gradient (<= 2.7e-6 of a dx_last row's max) and <= 0.01 on the terms against the float64 reference.
+worst |got - ref| / max|ref| (run with -s).  Worst fraction of the bound over the local cases on an MI355X (the dz cases included):
+0.11 on pooled, 0.03 on lat / z, 0.03 on every gradient, 0.05 on a dx_last row, below 0.01 on the terms.  (On the CPU the fp32 oracle
+itself sits at <= 0.65 of the bound on pooled, <= 0.10 on lat / z, <= 0.03 on every gradient and <= 0.01 on the terms.)
 """
 import ctypes as C
 
@@ -22,10 +24,12 @@ import torch
 
 from carel_vae_amd import _lib as L
 from carel_vae_amd import ops
+from tests.gpu_util import Guarded
 from tests.tail_restate import SCALED_BY_GRAD_OUT, TAIL_KEYS, hip_tail, oracle_tail, setup
 
 pytestmark = pytest.mark.gpu
 S, IT, SEED = 2, 7, 31
+RT_GRAD, AT_GRAD = 2e-4, 2e-5          # gradients: |got - ref| <= AT_GRAD max|ref| + RT_GRAD |ref| (dx_last: per row)
 TERMS = ((1, "mmd"), (2, "emo"), (3, "cau"), (4, "pair"), (5, "kl_e"), (6, "kl_c"), (7, "rec"), (8, "loss"))
 ERR_SHAPE = -2
 
@@ -71,8 +75,9 @@ def test_limit_table_follows_from_the_lds_formulas():
 
 
 # ---- cases
-def case(B, D=24, EC=6, V=257, dis="mmd", head="ce", p=0.5, allneg=False, grad_out=None):
-    return dict(B=B, D=D, EC=EC, V=V, dis=dis, head=head, p=p, allneg=allneg, grad_out=grad_out)
+def case(B, D=24, EC=6, V=257, dis="mmd", head="ce", p=0.5, allneg=False, grad_out=None, dz=False, lv=0.0):
+    """dz: the run gets an extra gradient on the sampled embeddings (make_dz); lv: added to two log-variance biases per side (large_log_var)."""
+    return dict(B=B, D=D, EC=EC, V=V, dis=dis, head=head, p=p, allneg=allneg, grad_out=grad_out, dz=dz, lv=lv)
 
 
 def _cases():
@@ -87,12 +92,45 @@ def _cases():
     c += [case(114, V=23771)]
     c += [case(38, D=32, allneg=True), case(38, D=32, allneg=True, p=0.0)]                  # dead pair head, train and eval
     c += [case(13, D=D, grad_out=2.5) for D in (24, 32)]
+    # dz_extra: 13 * 48 elements are three blocks of tail_add_dz_kernel with a partial last one, 13 * 14 less than one block
+    c += [case(B, dz=True) for B in (13, 65)] + [case(13, D=D, dz=True) for D in (7, 32)]
+    c += [case(B, dz=True, grad_out=2.5) for B in (13, 65)] + [case(13, D=D, dz=True, grad_out=0.0) for D in (24, 32)]
+    c += [case(13, dz=True, p=0.0), case(13, dz=True, p=0.0, grad_out=2.5)]                 # dropout off
+    c += [case(13, dz=True, lv=LV_LARGE, dis="none")]                                       # exp(lv) ~ 1e3: dz * eps * exp(lv) dominates d lat
     return c
 
 
 def case_id(c):
     s = "B%d-D%d-EC%d-V%d-%s-%s" % (c["B"], c["D"], c["EC"], c["V"], c["dis"], c["head"])
-    return s + ("-eval" if c["p"] == 0 else "") + ("-allneg" if c["allneg"] else "") + ("-gout" if c["grad_out"] else "")
+    s += ("-eval" if c["p"] == 0 else "") + ("-allneg" if c["allneg"] else "") + ("-gout" if c["grad_out"] else "")
+    return s + ("-gout0" if c["grad_out"] == 0.0 else "") + ("-dz" if c["dz"] else "") + ("-lv" if c["lv"] else "")
+
+
+LV_LARGE, LV_DIMS = 6.9, (0, 5)          # exp(6.9) = 992
+
+
+def large_log_var(P, D, lv):
+    """lv added to the log-variance biases of the coordinates LV_DIMS of both sides: z is ~1e3 there.  The heads and the decoder get
+    zero weights on those coordinates (a probability saturated at 0 or 1 has no finite gradient in the reference's BCE on
+    probabilities), so in d lat of those coordinates the routed dz * eps * exp(lv) stands beside the KL term alone."""
+    cols = list(LV_DIMS)
+    for k in ("emotion_log_var.bias", "cause_log_var.bias"):
+        P[k] = P[k].clone()
+        P[k][cols] += lv
+    for k in ("emotion_classifier.weight", "cause_classifier.weight"):
+        P[k] = P[k].clone()
+        P[k][:, cols] = 0.0
+    for k in ("pair_classifier.weight", "decoder.weight"):
+        P[k] = P[k].clone()
+        P[k][:, cols + [D + i for i in cols]] = 0.0
+
+
+def make_dz(B, D, seed, zero_row=1):
+    """The extra gradient on [z_e | z_c]: standard normal (both signs), row zero_row all zero (None: no such row)."""
+    dz = torch.randn((B, 2 * D), generator=torch.Generator().manual_seed(1000 + seed))
+    if zero_row is not None:
+        dz[zero_row] = 0.0
+    return dz
 
 
 CASES = _cases()
@@ -136,9 +174,11 @@ def outputs(buf, G):
     return [("pooled", buf.pooled), ("lat", buf.lat), ("z", buf.z), ("terms", buf.terms[:9]), ("dx_last", buf.dx_last)] + [(k, G[k]) for k in TAIL_KEYS]
 
 
-def check_local(rep, buf, G, ref, B, D, grad_out, rt, at):
+def check_local(rep, buf, G, ref, B, D, grad_out, rt, at, routed=None):
     """pooled / lat / z / terms / gradients / dx_last of one run against the float64 oracle.  rt / at: the gradient constants (atol is
-    at * max|ref|); dx_last per row."""
+    at * max|ref|); dx_last per row.  routed: (gradients, d x_last) of grad_out * loss + sum(z * dz) from the oracle, for a run with
+    dz_extra: what carel_tail_backward owns (SCALED_BY_GRAD_OUT, dx_last) is held against those as they are; the classifier and decoder
+    gradients stay carel_tail_losses' images for grad_out = 1, which dz does not reach."""
     out, pooled, grads, dx = ref
     go = 1.0 if grad_out is None else grad_out
     rep.cmp("pooled", buf.pooled, pooled, 1e-5, 5e-6)
@@ -148,10 +188,11 @@ def check_local(rep, buf, G, ref, B, D, grad_out, rt, at):
     for i, k in TERMS:
         rep.cmp(k, t[i], out[k], 1e-4, 1e-5, scale=max(abs(float(out[k])), 1e-30))
     for k in TAIL_KEYS:
-        r = (grads[k] if grads[k] is not None else torch.zeros_like(G[k].cpu()).double()) * (go if k in SCALED_BY_GRAD_OUT else 1.0)
+        src, f = (routed[0], 1.0) if routed is not None and k in SCALED_BY_GRAD_OUT else (grads, go if k in SCALED_BY_GRAD_OUT else 1.0)
+        r = (src[k] if src[k] is not None else torch.zeros_like(G[k].cpu()).double()) * f
         scale = float(r.abs().max()) + 1e-12
         rep.cmp(k, G[k], r, rt, at * scale + 1e-9)
-    check_dx(rep, buf.dx_last, dx * go, B, rt, at)
+    check_dx(rep, buf.dx_last, dx * go if routed is None else routed[1], B, rt, at)
 
 
 def check_dx(rep, got, ref, B, rt, at, name="dx_last"):
@@ -182,14 +223,31 @@ def test_tail_sweep(c):
     cfg, opt, P, x_last, batch, eps_e, eps_c = setup(B, S, V, seed=B + V + D, all_negative=c["allneg"], ec_dim=D, e_num_class=c["EC"],
                                                      disentangle=c["dis"], emotion_head=c["head"])
     pin_labels(batch, c["allneg"])
+    if c["lv"]:
+        large_log_var(P, D, c["lv"])
     train = c["p"] > 0
     assert c["p"] in (0.0, opt.dropout)
     ref = oracle_tail(P, x_last, batch, eps_e, eps_c, opt, B, S, IT, train, SEED, dtype=torch.float64)
+    dz = routed = None
+    if c["dz"]:
+        dz = make_dz(B, D, B + D)
+        routed = oracle_tail(P, x_last, batch, eps_e, eps_c, opt, B, S, IT, train, SEED, dtype=torch.float64, dz=dz, grad_out=c["grad_out"])[2:]
+    if c["lv"]:
+        assert all(float(ref[0][k][:, list(LV_DIMS)].exp().median()) > 500 for k in ("lv_e", "lv_c"))
     rep = Report(case_id(c))
-    buf, G = run_checked((P, x_last, batch, eps_e, eps_c, opt, B, S, V, IT, (c["p"], SEED, 0)), dict(grad_out=c["grad_out"]), rep)
-    check_local(rep, buf, G, ref, B, D, c["grad_out"], 2e-4, 2e-5)
+    args = (P, x_last, batch, eps_e, eps_c, opt, B, S, V, IT, (c["p"], SEED, 0))
+    buf, G = run_checked(args, dict(grad_out=c["grad_out"], dz_extra=dz), rep)
+    check_local(rep, buf, G, ref, B, D, c["grad_out"], RT_GRAD, AT_GRAD, routed=routed)
     if c["allneg"]:
         assert float(buf.terms[4]) == 0.0 and not bool(G["pair_classifier.weight"].any()) and not bool(G["pair_classifier.bias"].any())
+    if c["dz"] and c["grad_out"] == 0.0:
+        # only the routed part survives a loss scaled by 0: with dz = 0 as well, everything carel_tail_backward owns is exactly 0
+        # (the classifier and decoder images are not its to scale)
+        buf0, G0 = hip_tail(*args, grad_out=0.0, dz_extra=torch.zeros_like(dz))
+        for k in SCALED_BY_GRAD_OUT:
+            assert bool((G0[k] == 0).all()), (k, "not exactly 0 under grad_out = 0, dz = 0")
+        assert bool((buf0.dx_last == 0).all())
+        assert bool((G0["decoder.weight"] == G["decoder.weight"]).all()) and bool(G["decoder.weight"].any())
     rep.finish()
 
 
@@ -233,6 +291,69 @@ def test_tail_sweep_global_batch(R, Bl, D):
         scale = float(grads[k].abs().max()) + 1e-12
         rep.cmp(k, tot[k], grads[k], 3e-4, 3e-5 * scale)
     rep.finish()
+
+
+@pytest.mark.parametrize("grad_out", [None, 2.5])
+def test_tail_sweep_dz_batch_of_one(grad_out):
+    """dz_extra at a batch of ONE row.  carel_tail_losses takes such a batch only as one rank's shard of a global batch (its MMD
+    divides by n (n - 1)), so the case runs as two ranks of one pair each, in the layout of test_tail_sweep_global_batch, against the
+    oracle on the two pairs.  The test averages the ranks' gradients, so each rank routes R x its row of dz; neither row is zero (a
+    rank's whole dz would be), so both ranks run tail_add_dz_kernel on data."""
+    R, Bl, D, V = 2, 1, 24, 257
+    B = R * Bl
+    cfg, opt, P, x_last, batch, eps_e, eps_c = setup(B, S, V, seed=B + V + D, ec_dim=D)
+    pin_labels(batch, False)
+    dz = make_dz(B, D, B + D, zero_row=None)
+    out, pooled, grads, dx = oracle_tail(P, x_last, batch, eps_e, eps_c, opt, B, S, IT, True, SEED, dtype=torch.float64, dz=dz, grad_out=grad_out)
+    unit = oracle_tail(P, x_last, batch, eps_e, eps_c, opt, B, S, IT, True, SEED, dtype=torch.float64)[2]
+    rep = Report("dz-global-R%d-B%d-D%d%s" % (R, Bl, D, "-gout" if grad_out else ""))
+    shards = [({k: v[r * Bl:(r + 1) * Bl] for k, v in batch.items()}, x_last[r * Bl * S:(r + 1) * Bl * S]) for r in range(R)]
+    stride = Bl * 2 * D + 16
+    packed = torch.zeros((R, stride), device="cuda")
+    hooks = dict(global_label_sum=packed.view(-1)[Bl * 2 * D:], global_n=B, z_global=packed, mmd_grad_scale=float(R), global_rank_stride=stride,
+                 global_label_ranks=R)
+    for r, (sb, xl) in enumerate(shards):          # pass 1, for z alone (a batch of one needs the hooks even here; they hold zeros)
+        buf, _ = hip_tail(P, xl, sb, eps_e, eps_c, opt, Bl, S, V, IT, (opt.dropout, SEED, r * Bl), global_row_offset=r * Bl, **hooks)
+        packed[r, :Bl * 2 * D] = buf.z.reshape(-1)
+    for r, (sb, xl) in enumerate(shards):
+        packed[r, Bl * 2 * D] = float(sb["labels"].sum())
+    tot = {k: torch.zeros_like(v, dtype=torch.float64) for k, v in P.items()}
+    for r, (sb, xl) in enumerate(shards):
+        kw = dict(hooks, global_row_offset=r * Bl, grad_out=grad_out, dz_extra=R * dz[r * Bl:(r + 1) * Bl])
+        buf, G = run_checked((P, xl, sb, eps_e, eps_c, opt, Bl, S, V, IT, (opt.dropout, SEED, r * Bl)), kw, rep)
+        check_dx(rep, buf.dx_last / R, dx[r * Bl * S:(r + 1) * Bl * S], Bl, RT_GRAD, AT_GRAD, "dx%d" % r)
+        for k in tot:
+            tot[k] += G[k].double().cpu() / R
+    for k in TAIL_KEYS:
+        r = grads[k] if k in SCALED_BY_GRAD_OUT else unit[k]
+        rep.cmp(k, tot[k], r, RT_GRAD, AT_GRAD * (float(r.abs().max()) + 1e-12) + 1e-9)
+    rep.finish()
+
+
+# ---- carel_scale_f32
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 2048 * 256, 2048 * 256 + 3])
+def test_scale_is_one_rounding(n):
+    """x *= s in place with s a device scalar: the bits of torch float32's x * s (one rounding), for s = 0 (signed zeros), 1, 2 and a
+    scale that rounds; past 2048 blocks x 256 threads the grid-stride loop takes a second trip; the guard regions around the range
+    keep their fill.  Then the refusals: a null range, a null scale and n = 0 return an error and write nothing."""
+    lib, st = L.load(), L.current_stream()
+    gen = torch.Generator().manual_seed(n % 1000)
+    x = torch.randn(n, generator=gen)
+    for s in (0.0, 1.0, 2.0, -0.37):
+        g = Guarded((n,), torch.float32, None, gen)
+        g.t.copy_(x)
+        sd = torch.tensor([s], dtype=torch.float32, device="cuda")
+        L.check(lib.carel_scale_f32(g.ptr, n, sd.data_ptr(), st), "carel_scale_f32")
+        torch.cuda.synchronize()
+        assert g.intact(), (n, s, "guard region written")
+        assert torch.equal(bits(g.t.cpu()), bits(x * torch.tensor(s, dtype=torch.float32))), (n, s)
+    g = Guarded((n,), torch.float32, None, gen)
+    g.t.copy_(x)
+    sd = torch.tensor([2.0], dtype=torch.float32, device="cuda")
+    for bad in ((None, n, sd.data_ptr()), (g.ptr, n, None), (g.ptr, 0, sd.data_ptr())):
+        assert lib.carel_scale_f32(bad[0], bad[1], bad[2], st) != 0
+    torch.cuda.synchronize()
+    assert g.intact() and torch.equal(bits(g.t.cpu()), bits(x))
 
 
 # ---- refusals

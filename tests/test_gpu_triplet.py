@@ -14,6 +14,7 @@ from oracle import carel_oracle as O
 from oracle import carel_oracle_st as ST
 
 pytestmark = pytest.mark.gpu
+TOL_GRAD_WORST, TOL_GRAD_MEDIAN = 6e-2, 2e-2        # encoder gradients per tensor against the fp32 restatement's autograd: worst, median
 
 
 def relnorm(a, b):
@@ -230,7 +231,7 @@ def test_first_step_gradients_and_clip_norm_against_the_restatement(variant):
         if gr is None or float(gr.norm()) < 1e-7:
             continue
         worst[k] = relnorm(named[_public(model, k)].grad, gr)
-    assert max(worst.values()) < 6e-2 and float(np.median(list(worst.values()))) < 2e-2, sorted(worst.items(), key=lambda kv: -kv[1])[:3]
+    assert max(worst.values()) < TOL_GRAD_WORST and float(np.median(list(worst.values()))) < TOL_GRAD_MEDIAN, sorted(worst.items(), key=lambda kv: -kv[1])[:3]
     opt = S.FusedAdamW(model, lr=1e-3)
     opt.step()
     total = float(torch.sqrt(sum((Wr[k].grad.double() ** 2).sum() for k in keys if Wr[k].grad is not None)))

@@ -12,6 +12,7 @@ from carel_vae_amd import ops
 from oracle import carel_oracle as O
 
 pytestmark = pytest.mark.gpu
+TOL_APRX_GRAD = 2e-5        # approximation-network gradients of carel_vi_aprx against the fp32 oracle on the same z: |d| <= TOL max(max|ref|, 1e-3)
 
 
 def _net(opt, seed):
@@ -34,7 +35,7 @@ def test_vi_kernels_vs_oracle(B, D):
     np.testing.assert_allclose(float(loss), float(ref.detach()), rtol=2e-5)
     for k, g in zip(O.VI_KEYS, grads):
         r = leaf[k].grad
-        assert float((g.cpu() - r).abs().max()) <= 2e-5 * max(float(r.abs().max()), 1e-3), k
+        assert float((g.cpu() - r).abs().max()) <= TOL_APRX_GRAD * max(float(r.abs().max()), 1e-3), k
     # CLUB bound + gradient wrt the embeddings
     up, dz = ops.vi_upper(z.cuda(), net, perm.cuda())
     ze, zc = z[:, :D].clone().requires_grad_(True), z[:, D:].clone().requires_grad_(True)
