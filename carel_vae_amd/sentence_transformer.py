@@ -360,7 +360,16 @@ class SentenceTransformer(nn.Module):
         tt = features.get("token_type_ids")
         lens = features.get("seq_lengths")
         if lens is None:
-            lens = att.sum(1).tolist()                        # host list (one read-back; loaders that know the lengths pass them)
+            # host list (one read-back; loaders that know the lengths pass them) with `prefix` riding along as in _pack_info: packing and
+            # mean_pool_fwd take the FIRST len tokens of a sentence, so a left-padded mask or one with a hole would pool other tokens
+            msk = att.to(torch.int32)
+            n = msk.sum(1)
+            prefix = ((torch.arange(msk.shape[1], device=dev)[None, :] < n[:, None]).to(torch.int32) == msk).all()
+            info = torch.cat((n, prefix.to(torch.int32).reshape(1))).tolist()
+            lens = info[:-1]
+            if not info[-1]:
+                raise L.CarelError("SentenceTransformer: the attention mask must be right-padded (ones first, then zeros, in every row): "
+                                   "pooling reads the first sum(mask) tokens of a sentence; left-padded masks and masks with holes are refused")
         lens = [int(v) for v in lens]
         c = m._prepare_inputs(ids, att, None if tt is None else tt.to(dev), lens)
         c.lens = lens
@@ -417,7 +426,8 @@ class SentenceTransformer(nn.Module):
         m._bind_grads()
 
     def forward(self, features):
-        """features: {"input_ids", "attention_mask", "token_type_ids"} -> the same dict plus "sentence_embedding" [B, 768]."""
+        """features: {"input_ids", "attention_mask", "token_type_ids"} -> the same dict plus "sentence_embedding" [B, 768].  The mask
+        must be right-padded (HF padding_side "right"); any other mask is refused (_make_call)."""
         c = self._make_call(features)
         if torch.is_grad_enabled():
             anchor = self._m._flat.new_zeros((), requires_grad=True)

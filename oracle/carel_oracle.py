@@ -584,13 +584,17 @@ def forward_terms(P, batch: Dict[str, torch.Tensor], iteration: int, cfg: Encode
     return out
 
 
+def pair_latents(P, ids, att, tt, cfg, opt, quant: Quant = None):
+    """The deterministic front of `get_pair_preds` (:265-276): eval-mode encoder, pooler, the four latent heads ->
+    [N, 4 * ec_dim] = [mu_e | log_var_e | mu_c | log_var_c] (the layout of DrlClassifier.pair_latents)."""
+    pooled = encoder_forward(P, ids, att, tt, cfg, quant=quant)
+    return torch.cat([pooled @ P[n + ".weight"].t() + P[n + ".bias"] for n in ("emotion_mu", "emotion_log_var", "cause_mu", "cause_log_var")],
+                     dim=1)
+
+
 def pair_preds(P, ids, att, tt, cfg, opt, eps_e, eps_c, quant: Quant = None):
     """`get_pair_preds` (:265-282): eval-mode encoder, fresh noise (quirk Q6), round(sigmoid)."""
-    pooled = encoder_forward(P, ids, att, tt, cfg, quant=quant)
-    mu_e = pooled @ P["emotion_mu.weight"].t() + P["emotion_mu.bias"]
-    lv_e = pooled @ P["emotion_log_var.weight"].t() + P["emotion_log_var.bias"]
-    mu_c = pooled @ P["cause_mu.weight"].t() + P["cause_mu.bias"]
-    lv_c = pooled @ P["cause_log_var.weight"].t() + P["cause_log_var.bias"]
+    mu_e, lv_e, mu_c, lv_c = pair_latents(P, ids, att, tt, cfg, opt, quant=quant).split(opt.ec_dim, dim=1)
     z = torch.cat((mu_e + eps_e * lv_e.exp(), mu_c + eps_c * lv_c.exp()), dim=1)
     prob = torch.sigmoid(z @ P["pair_classifier.weight"].t() + P["pair_classifier.bias"])
     return prob

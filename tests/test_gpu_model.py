@@ -361,15 +361,33 @@ def test_get_pair_preds_and_cpu_refusal(golden_dir):
     cfg, opt = CASES["zh_ragged"]
     z, batch = load(golden_dir, "zh_ragged")
     B, S, Lr, vocab, V, wseed, bseed, steps, it0 = (int(v) for v in z["meta"])
+    from tests import eval_restate as R
     model, P = build(cfg, opt, wseed)
     model.eval()
-    eps_e, eps_c = torch.randn(24), torch.randn(24)
+    g = torch.Generator().manual_seed(360)
+    eps_e, eps_c = torch.randn(24, generator=g), torch.randn(24, generator=g)
+    ids, att, tt = batch["input_ids"], batch["attention_masks"], batch["token_type_ids"]
+    # as initialised the oracle's probabilities sit in 0.41 .. 0.56 and 14 of 16 rows round to 0, which a constant-0 predictor gets right:
+    # pair head x 8 and a bias at the oracle's median logit put the oracle's own rounded classes on both sides
+    with torch.no_grad():
+        P = R.calibrate(P, O.pair_latents(P, ids, att, tt, cfg, opt), eps_e, eps_c)
+    model.load_state_dict(P)
     model.set_noise(eps_e, eps_c)
-    preds = model.get_pair_preds(batch["input_ids"].cuda(), batch["attention_masks"].cuda(), batch["token_type_ids"].cuda())
+    preds = model.get_pair_preds(ids.cuda(), att.cuda(), tt.cuda())
     assert isinstance(preds, list) and len(preds) == B and preds[0][0] in (0.0, 1.0)
-    prob = O.pair_preds(P, batch["input_ids"], batch["attention_masks"], batch["token_type_ids"], cfg, opt, eps_e, eps_c).squeeze(1)
+    with torch.no_grad():
+        prob = O.pair_preds(P, ids, att, tt, cfg, opt, eps_e, eps_c).squeeze(1)
     far = (prob - 0.5).abs() > 2e-2
     assert torch.equal(torch.tensor(preds).squeeze(1)[far], prob.round()[far])
+    assert set(prob.round()[far].tolist()) == {0.0, 1.0} and int(far.sum()) >= B * 3 // 4      # both classes among the compared rows
+    # the unrounded probabilities: a float64 sigmoid of the oracle's latents under the same noise (tests/eval_restate.py: TOL_PROB)
+    with torch.no_grad():
+        want = R.pair_prob(O.pair_latents(P, ids, att, tt, cfg, opt), P, eps_e, eps_c)
+    model.set_noise(eps_e, eps_c)
+    raw = torch.tensor(model.get_pair_preds(ids.cuda(), att.cuda(), tt.cuda(), round=False), dtype=torch.float64).reshape(-1)
+    assert float((raw - want).abs().max()) <= R.TOL_PROB
+    model.set_noise(eps_e, eps_c)
+    assert float((model.pair_probabilities(ids.cuda(), att.cuda(), tt.cuda(), chunk=8).double().cpu() - want).abs().max()) <= R.TOL_PROB
     with pytest.raises(M.L.CarelError):
         model.get_pair_preds(batch["input_ids"], batch["attention_masks"], batch["token_type_ids"])   # CPU tensors
 
