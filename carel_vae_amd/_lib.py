@@ -61,6 +61,22 @@ class MmdPermArgs(C.Structure):
 PERM_MAX_N, PERM_MAX_PERMUTATIONS = 8192, 65535
 
 
+class HsicGramArgs(C.Structure):
+    """carel_hsic_gram_args (include/carel_hip.h)."""
+    _fields_ = [("x", C.c_void_p), ("ldx", C.c_int64), ("m", C.c_int32), ("d", C.c_int32), ("s", C.c_float), ("k_out", C.c_void_p),
+                ("ldk", C.c_int64)]
+
+
+class HsicPermArgs(C.Structure):
+    """carel_hsic_perm_args (include/carel_hip.h)."""
+    _fields_ = [("k", C.c_void_p), ("ldk", C.c_int64), ("l", C.c_void_p), ("ldl", C.c_int64), ("perms", C.c_void_p),
+                ("m", C.c_int32), ("n_permutations", C.c_int32),
+                ("stats", C.c_void_p), ("count", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+HSIC_PERM_MAX_M = 8192
+
+
 class EmbedArgs(C.Structure):
     _fields_ = [("input_ids", C.c_void_p), ("token_type_ids", C.c_void_p),
                 ("word_emb", C.c_void_p), ("pos_emb", C.c_void_p), ("type_emb", C.c_void_p),
@@ -283,6 +299,9 @@ SIGNATURES = {
     "carel_pdist_bwd": (C.c_int, [C.POINTER(PdistArgs), C.c_void_p]),
     "carel_hsic_fwd": (C.c_int, [C.POINTER(HsicArgs), C.c_void_p]),
     "carel_hsic_bwd": (C.c_int, [C.POINTER(HsicArgs), C.c_void_p]),
+    "carel_hsic_gram": (C.c_int, [C.POINTER(HsicGramArgs), C.c_void_p]),
+    "carel_hsic_perm_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "carel_hsic_perm_test": (C.c_int, [C.POINTER(HsicPermArgs), C.c_void_p]),
     "carel_selftest_layouts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "carel_embed_ln_fwd": (C.c_int, [C.POINTER(EmbedArgs), C.c_void_p]),
     "carel_embed_ln_bwd_blocks": (C.c_int, [C.c_int64]),

@@ -475,6 +475,87 @@ def mmd_two_sample_test(sample_1, sample_2, alphas, n_permutations=1000, eps=1e-
     return (mmd, pval, stats, count) if return_stats else (mmd, pval)
 
 
+def random_permutations(m, n_permutations, device, generator=None):
+    """int32 [n_permutations + 1, m] on `device`: the identity first (the observed pairing), then uniformly random permutations of
+    0..m-1 -- the stable argsort of uniform draws, so a seeded generator repeats them (the draws are made on the generator's own
+    device)."""
+    m, P = int(m), int(n_permutations)
+    perms = torch.empty((P + 1, m), dtype=torch.int32, device=device)
+    perms[0] = torch.arange(m, dtype=torch.int32, device=device)
+    u = torch.rand((P, m), generator=generator, device=device if generator is None else generator.device)
+    perms[1:] = torch.argsort(u, dim=1, stable=True).to(device, torch.int32)
+    return perms
+
+
+def _checked_permutations(who, permutations, P, m, dev):
+    """int32 [P, m] on `dev`, or CarelError: the shape and the dtype on the host, then -- one reduction and one read-back -- every sorted
+    row against arange(m) on the device"""
+    pm = torch.as_tensor(permutations)
+    if pm.dtype not in (torch.int32, torch.int64) or tuple(pm.shape) != (P, m):
+        raise L.CarelError("%s: permutations must be int32 or int64 [n_permutations, m]" % who)
+    pm = pm.to(dev)
+    if not bool((torch.sort(pm, dim=1).values == torch.arange(m, device=dev, dtype=pm.dtype)).all()):
+        raise L.CarelError("%s: every row of permutations must be a permutation of 0..m-1" % who)
+    return pm.to(torch.int32)
+
+
+def hsic_permutation_test(K, L_, n_permutations=1000, *, permutations=None, generator=None, return_stats=False, _checked=False):
+    """The permutation independence test of Gretton et al. (2007) on two kernel matrices; THE DEFINITION IS THIS PROJECT'S OWN
+    (include/carel_hip.h, carel_hsic_perm_test; the reference has no such function, the statistic is its HSIC).  With Kc = H K H,
+    stat(pi) = sum_ij Kc[i, j] L[pi_i, pi_j] / (m-1)^2; the p-value is the share of the n_permutations re-pairings whose statistic is
+    >= the observed one's (pi = identity, not itself among them).  K, L: [m, m] CUDA tensors, CPU tensors or ndarrays (they go to the
+    device as float32), 2 <= m <= 8192.  permutations: int32 / int64 [n_permutations, m] re-pairings (default: `random_permutations`
+    from `generator`); they are validated on the device -- every sorted row must equal arange(m) -- which costs one reduction and one
+    read-back before the test is launched.  Returns a Python float, with return_stats (pval, stats float64 [n_permutations + 1] on
+    the device, count)."""
+    if not torch.cuda.is_available():
+        raise L.CarelError("hsic_permutation_test runs on the GPU (carel_hsic_perm_test); there is no CPU fallback.")
+    k, l = torch.as_tensor(K).detach(), torch.as_tensor(L_).detach()
+    dev = k.device if k.is_cuda else (l.device if l.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    k, l = k.to(dev, torch.float32), l.to(dev, torch.float32)
+    P = int(n_permutations)
+    if k.dim() != 2 or k.shape[0] != k.shape[1] or tuple(l.shape) != tuple(k.shape):
+        raise L.CarelError("hsic_permutation_test: K and L must both be [m, m]")
+    m = k.shape[0]
+    if not 2 <= m <= L.HSIC_PERM_MAX_M or not 1 <= P <= L.PERM_MAX_PERMUTATIONS:
+        raise L.CarelError("hsic_permutation_test: 2 <= m <= %d and 1 <= n_permutations <= %d are required"
+                           % (L.HSIC_PERM_MAX_M, L.PERM_MAX_PERMUTATIONS))
+    k, l = (t if t.stride(1) == 1 else t.contiguous() for t in (k, l))
+    with torch.cuda.device(dev):
+        if permutations is None:
+            full = random_permutations(m, P, dev, generator)
+        else:
+            pm = permutations if _checked else _checked_permutations("hsic_permutation_test", permutations, P, m, dev)
+            full = torch.cat((torch.arange(m, device=dev, dtype=torch.int32)[None], pm), 0)
+        stats, count = ops.hsic_perm_test(k, l, full)
+        c = int(count.item())
+    pval = c / P
+    return (pval, stats, c) if return_stats else pval
+
+
+def hsic_independence_test(x, y, s_x=1.0, s_y=1.0, n_permutations=1000, *, permutations=None, generator=None, return_stats=False):
+    """The independence test from the paired samples x [m, d_x], y [m, d_y] (the widths may differ): the tiled Gram matrices
+    K = exp(-D(x) / s_x), L = exp(-D(y) / s_y) (carel_hsic_gram, 2 <= m <= 8192), then `hsic_permutation_test`.  Returns (hsic, pval)
+    as Python floats -- hsic is the observed statistic, what `HSIC(x, y, s_x, s_y)` computes, and above that operator's row limit
+    (757 at d = 24) this is the only way to it -- and with return_stats (hsic, pval, stats, count)."""
+    if not torch.cuda.is_available():
+        raise L.CarelError("hsic_independence_test runs on the GPU (carel_hsic_gram, carel_hsic_perm_test); there is no CPU fallback.")
+    xs, ys = torch.as_tensor(x).detach(), torch.as_tensor(y).detach()
+    dev = xs.device if xs.is_cuda else (ys.device if ys.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    xs, ys = xs.to(dev, torch.float32), ys.to(dev, torch.float32)
+    if xs.dim() != 2 or ys.dim() != 2 or xs.shape[0] != ys.shape[0]:
+        raise L.CarelError("hsic_independence_test: two samples [m, d_x], [m, d_y] of the same number of rows are required")
+    xs, ys = (s if s.stride(1) == 1 else s.contiguous() for s in (xs, ys))
+    with torch.cuda.device(dev):
+        if permutations is not None:         # refused before the Gram launches, not after them
+            permutations = _checked_permutations("hsic_independence_test", permutations, int(n_permutations), xs.shape[0], dev)
+        kx, ky = ops.hsic_gram(xs, s_x), ops.hsic_gram(ys, s_y)
+    pval, stats, count = hsic_permutation_test(kx, ky, n_permutations, permutations=permutations, generator=generator, return_stats=True,
+                                               _checked=permutations is not None)
+    hsic = float(stats[0])
+    return (hsic, pval, stats, count) if return_stats else (hsic, pval)
+
+
 class _PdistFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, s1, s2, eps):
@@ -1483,6 +1564,20 @@ class DrlClassifier(nn.Module):
         z = ops.sample_latents(lat, eps_e[0].contiguous(), eps_c[0].contiguous(), D)
         return mmd_two_sample_test(z[:, :D], z[:, D:], ops.MODEL_MMD_ALPHAS if alphas is None else alphas, n_permutations, eps=1e-5,
                                    labels=labels, generator=generator, return_stats=return_stats)
+
+    def latent_independence_test(self, lat, n_permutations=1000, noise=None, s_e=1.0, s_c=1.0, permutations=None, generator=None,
+                                 return_stats=False):
+        """Are the emotion and the cause latent of the same pair independent (extension)?  The permutation independence test of
+        `hsic_independence_test` on z_e, z_c [N, ec_dim] sampled from the latents of `pair_latents` exactly as
+        `latent_two_sample_test` samples them (noise = (eps_e, eps_c) replays a chosen draw; without it one is drawn like a forward
+        call's).  s_e, s_c: the kernel widths of the two Gram matrices.  N <= 8192.  Returns (hsic, pval), with return_stats
+        (hsic, pval, stats, count)."""
+        self._require_cuda()
+        D = self.opt.ec_dim
+        eps_e, eps_c = self._draws_noise(lat.device, 1, noise)
+        z = ops.sample_latents(lat, eps_e[0].contiguous(), eps_c[0].contiguous(), D)
+        return hsic_independence_test(z[:, :D], z[:, D:], s_e, s_c, n_permutations, permutations=permutations, generator=generator,
+                                      return_stats=return_stats)
 
     def draw_counts(self, lat, labels, n_draws, groups=None, noise=None, return_noise=False, n_groups=None):
         """int64 [K, G, 3]: TP / FP / FN of `prob > 0.5` (numpy's .round() of a probability, ref :282: exactly 0.5 predicts 0) against

@@ -506,3 +506,6 @@ class DrlClassifier(_Base):
         raise L.CarelError("pair_latents / pair_probabilities_from / draw_counts cover the two-space models; this model has pair_logits")
 
     pair_probabilities_from = draw_counts = pair_latents
+
+    def latent_independence_test(self, *a, **k):
+        raise L.CarelError("latent_independence_test covers the two-space models (the latents of pair_latents); this model has pair_logits")

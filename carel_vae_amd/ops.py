@@ -523,6 +523,45 @@ def hsic(x, y, s_x=1.0, s_y=1.0):
     return out
 
 
+def hsic_gram(x, s=1.0):
+    """carel_hsic_gram: K = exp(-D(x) / s) f32 [m, m] of the rows of x f32 [m, d], tiled (2 <= m <= 8192, d <= 64): the kernel matrix
+    of `hsic`, element by element the same expression, bitwise symmetric, diagonal exactly 1."""
+    _chk_cuda(x)
+    if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1:
+        raise L.CarelError("hsic_gram: a float32 [m, d] sample with contiguous rows is required")
+    m = x.shape[0]
+    out = torch.empty((m, m), device=x.device, dtype=torch.float32)
+    a = L.HsicGramArgs()
+    a.x, a.ldx, a.m, a.d, a.s, a.k_out, a.ldk = x.data_ptr(), x.stride(0), m, x.shape[1], float(s), out.data_ptr(), m
+    L.check(L.load().carel_hsic_gram(C.byref(a), L.current_stream()), "carel_hsic_gram")
+    return out
+
+
+def hsic_perm_test(K, Lm, perms):
+    """carel_hsic_perm_test: K, Lm f32 [m, m] (rows contiguous), perms int32 [P+1, m] whose row 0 is the observed pairing (the
+    identity).  Returns (stats f64 [P+1], count int32 [1]) on the device; nothing is read back."""
+    _chk_cuda(K, Lm, perms)
+    m = K.shape[0] if K.dim() == 2 else -1
+    if any(t.dtype != torch.float32 or t.dim() != 2 or tuple(t.shape) != (m, m) or t.stride(1) != 1 for t in (K, Lm)):
+        raise L.CarelError("hsic_perm_test: K and L must be float32 [m, m] with contiguous rows")
+    if perms.dtype != torch.int32 or perms.dim() != 2 or perms.shape[1] != m or perms.shape[0] < 2 or not perms.is_contiguous():
+        raise L.CarelError("hsic_perm_test: perms must be contiguous int32 [n_permutations + 1, m]")
+    if Lm.device != K.device or perms.device != K.device:
+        raise L.CarelError("hsic_perm_test: the matrices and the permutations are on different devices")
+    P = perms.shape[0] - 1
+    lib = L.load()
+    a = L.HsicPermArgs()
+    a.k, a.ldk, a.l, a.ldl, a.perms = K.data_ptr(), K.stride(0), Lm.data_ptr(), Lm.stride(0), perms.data_ptr()
+    a.m, a.n_permutations = m, P
+    stats = torch.empty(P + 1, device=K.device, dtype=torch.float64)
+    count = torch.empty(1, device=K.device, dtype=torch.int32)
+    nbytes = int(lib.carel_hsic_perm_workspace_bytes(m, P))
+    work = torch.empty(max(nbytes, 8) // 8, device=K.device, dtype=torch.float64)
+    a.stats, a.count, a.workspace, a.workspace_bytes = stats.data_ptr(), count.data_ptr(), work.data_ptr(), nbytes
+    L.check(lib.carel_hsic_perm_test(C.byref(a), L.current_stream()), "carel_hsic_perm_test")
+    return stats, count
+
+
 def hsic_backward(x, y, grad, s_x=1.0, s_y=1.0):
     a = _hsic_args(x, y, s_x, s_y)
     gx, gy = torch.empty(x.shape, device=x.device, dtype=torch.float32), torch.empty(y.shape, device=x.device, dtype=torch.float32)

@@ -825,6 +825,61 @@ typedef struct carel_hsic_args {
 int carel_hsic_fwd(const carel_hsic_args* args, void* stream);
 int carel_hsic_bwd(const carel_hsic_args* args, void* stream);
 
+/* The Gram matrix of HSIC alone, tiled: k_out[i][j] = K_ij = exp(-D(x)_ij / s) f32 [m, m] (row stride ldk >= m; the padding is not
+ * written), each element by the expression carel_hsic_fwd evaluates (hsic_kern of csrc/hsic_device.h: the norms and the dot product by
+ * the same fmaf chains, __expf(-(n_i + n_j - 2 dot) / s)), so the matrix is bitwise symmetric and its diagonal is exactly 1.
+ * carel_hsic_fwd keeps both samples in one workgroup's LDS and stops at m = 757 (d = 24); this one holds 128 rows per workgroup
+ * whatever m is.  1 <= d <= 64, 2 <= m <= 8192, ldx >= d, s > 0.  One launch.  Errors before it: a NULL struct / x / k_out, ldx < d,
+ * ldk < m, s <= 0 -> CAREL_ERR_ARG; m or d outside the limits -> CAREL_ERR_SHAPE.  (carel_rbf_gram evaluates the MMD form,
+ * sum_a exp(-alpha_a (eps + |d2|)), and cannot serve here.) */
+typedef struct carel_hsic_gram_args {
+  const void* x;            /* f32 [m, d], row stride ldx */
+  int64_t ldx;
+  int32_t m, d;
+  float s;                  /* kernel width, 1 in the reference */
+  void* k_out;              /* f32 [m, m], row stride ldk */
+  int64_t ldk;
+} carel_hsic_gram_args;
+int carel_hsic_gram(const carel_hsic_gram_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Permutation independence test on two kernel matrices (Gretton et al. 2007): the HSIC value of m paired rows and the share of random
+ * re-pairings whose HSIC reaches it.  The reference has no such function, so this DEFINITION IS THE PROJECT'S OWN (parity unpinned);
+ * the statistic itself is the reference's HSIC (drl_classifier_ec_hsic.py:540-547).
+ *   K, L f32 [m, m], row strides ldk, ldl >= m, not necessarily symmetric, diagonal included;
+ *   R_i, C_j, T the row sums, column sums and total of K;  Kc_ij = K_ij - R_i/m - C_j/m + T/m^2 = (H K H)_ij;
+ *   for a permutation pi of 0..m-1:  stat(pi) = sum_ij Kc_ij L[pi_i][pi_j] / (m-1)^2  (the identity on the Gram matrices of x and y:
+ *   tr(L H K H) / (m-1)^2, what carel_hsic_fwd computes);
+ *   perms i32 [P+1, m] contiguous, row 0 = the observed pairing (the caller sets it to the identity), rows 1..P the re-pairings.  Every
+ *   index is clamped into [0, m) before it addresses anything: a row that is no permutation gives a wrong statistic, never an access
+ *   outside the matrices -- the CALLER sees to it that each row is a permutation;
+ *   stats f64 [P+1] = stat of every row;  count i32 [1] = #{p in 1..P : stats[p] >= stats[0]}, compared on the doubles on the device;
+ *   p-value = count / P (the observed pairing is not among the P).
+ * R, C, T are summed in double and Kc_ij is formed in double and rounded to f32 once; the products Kc_ij L[pi_i][pi_j] are exact in
+ * double and every sum is double, in an order fixed by indices: no atomics, equal rows of `perms` give equal bits wherever they stand,
+ * and so do two runs (csrc/hsic_perm.hip; the bound: tests/hsic_perm_restate.py).
+ * workspace: carel_hsic_perm_workspace_bytes(m, P) bytes of device memory, 16-byte aligned, fully rewritten by every call; the
+ * function is pure host code and returns 0 for a shape outside the limits.
+ * Limits: 2 <= m <= 8192, 1 <= P <= 65535.  Eight launches on `stream`, no allocation, no host synchronisation.
+ * Errors before the first launch: a NULL struct / k / l / perms / stats / count / workspace, ldk or ldl < m, a workspace smaller than
+ * stated or not 16-byte aligned -> CAREL_ERR_ARG; m or P outside the limits -> CAREL_ERR_SHAPE.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct carel_hsic_perm_args {
+  const void* k;            /* f32 [m, m], row stride ldk */
+  int64_t ldk;
+  const void* l;            /* f32 [m, m], row stride ldl */
+  int64_t ldl;
+  const void* perms;        /* i32 [P+1, m] */
+  int32_t m;
+  int32_t n_permutations;   /* P */
+  void* stats;              /* f64 [P+1] */
+  void* count;              /* i32 [1] */
+  void* workspace;
+  int64_t workspace_bytes;
+} carel_hsic_perm_args;
+int64_t carel_hsic_perm_workspace_bytes(int32_t m, int32_t n_permutations);
+int carel_hsic_perm_test(const carel_hsic_perm_args* args, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * VI / CLUB head (ablation script drl_classifier_ec_vi.py).  z = [e | c] f32 [B, 2*ec_dim] are the sampled emotion /
  * cause embeddings; net[8] = approximation network p(e|c): ec_mu.0.weight, ec_mu.0.bias, ec_mu.2.weight, ec_mu.2.bias,
