@@ -9,11 +9,11 @@ C ABI of include/carel_hip.h.  There is no CPU / eager fallback.
 from . import _lib  # noqa: F401
 from .data import BatchLoader, PrefetchLoader, ECPEDataset, get_bow_en, get_bow_zh, newsplit_paths, read_ECPE_data  # noqa: F401
 from .drl_classifier import (HSIC, DrlClassifier, FusedAdam, FusedRMSprop, MMDStatistic, encoder_config, hsic_independence_test,  # noqa: F401
-                             hsic_permutation_test, make_gan_opt, make_newsplit_opt, make_opt, mmd_two_sample_test, pdist,
-                             permutation_test_mat, random_labellings, random_permutations)
+                             hsic_permutation_test, make_gan_opt, make_newsplit_opt, make_opt, median_alphas, median_heuristic,
+                             mmd_two_sample_test, pdist, pdist_quantile, permutation_test_mat, random_labellings, random_permutations)
 from . import drl_classifier_en  # noqa: F401   the three-space adversarial model of drl_classifier_en.py (same class name: DrlClassifier)
 from .training import generate_self_train_data, load_ckp, prf_from_counts, save_ckp, train  # noqa: F401
 
-__all__ = ["ECPEDataset", "BatchLoader", "PrefetchLoader", "DrlClassifier", "MMDStatistic", "pdist", "HSIC", "permutation_test_mat", "mmd_two_sample_test", "random_labellings", "hsic_permutation_test", "hsic_independence_test", "random_permutations", "read_ECPE_data", "train",
+__all__ = ["ECPEDataset", "BatchLoader", "PrefetchLoader", "DrlClassifier", "MMDStatistic", "pdist", "HSIC", "permutation_test_mat", "mmd_two_sample_test", "random_labellings", "hsic_permutation_test", "hsic_independence_test", "random_permutations", "pdist_quantile", "median_heuristic", "median_alphas", "read_ECPE_data", "train",
            "generate_self_train_data", "save_ckp", "load_ckp", "get_bow_zh", "get_bow_en", "FusedAdam", "FusedRMSprop", "make_opt", "make_gan_opt",
            "encoder_config", "make_newsplit_opt", "newsplit_paths", "prf_from_counts"]

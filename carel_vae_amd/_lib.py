@@ -77,6 +77,16 @@ class HsicPermArgs(C.Structure):
 HSIC_PERM_MAX_M = 8192
 
 
+class PdistSelectArgs(C.Structure):
+    """carel_pdist_select_args (include/carel_hip.h)."""
+    _fields_ = [("x", C.c_void_p), ("ldx", C.c_int64), ("m", C.c_int32), ("d", C.c_int32), ("n_ranks", C.c_int32),
+                ("ranks", C.c_int64 * 8), ("values", C.c_void_p), ("counts", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+PDIST_SELECT_MAX_RANKS = 8
+
+
 class EmbedArgs(C.Structure):
     _fields_ = [("input_ids", C.c_void_p), ("token_type_ids", C.c_void_p),
                 ("word_emb", C.c_void_p), ("pos_emb", C.c_void_p), ("type_emb", C.c_void_p),
@@ -302,6 +312,8 @@ SIGNATURES = {
     "carel_hsic_gram": (C.c_int, [C.POINTER(HsicGramArgs), C.c_void_p]),
     "carel_hsic_perm_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "carel_hsic_perm_test": (C.c_int, [C.POINTER(HsicPermArgs), C.c_void_p]),
+    "carel_pdist_select_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "carel_pdist_select": (C.c_int, [C.POINTER(PdistSelectArgs), C.c_void_p]),
     "carel_selftest_layouts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "carel_embed_ln_fwd": (C.c_int, [C.POINTER(EmbedArgs), C.c_void_p]),
     "carel_embed_ln_bwd_blocks": (C.c_int, [C.c_int64]),

@@ -11,10 +11,16 @@ namespace carel {
 
 struct HsicCfg { int m, d, xs; float inv_sx, inv_sy; };   // xs = LDS row stride (odd)
 
-__device__ __forceinline__ float hsic_kern(const float* X, const float* nrm, int i, int j, int d, int xs, float inv_s) {
+// D_ij, the argument of hsic_kern before the width: symmetric in i and j to the bit, and exactly +0 where dot is the norm's own chain
+// (i = j).  Slightly negative for near-duplicate rows far from the origin (no abs).  pdist_select.hip ranks these values.
+__device__ __forceinline__ float hsic_sqdist(const float* X, const float* nrm, int i, int j, int d, int xs) {
   float dot = 0.f;
   for (int k = 0; k < d; ++k) dot = fmaf(X[i * xs + k], X[j * xs + k], dot);
-  return __expf(-(nrm[i] + nrm[j] - 2.0f * dot) * inv_s);
+  return nrm[i] + nrm[j] - 2.0f * dot;
+}
+
+__device__ __forceinline__ float hsic_kern(const float* X, const float* nrm, int i, int j, int d, int xs, float inv_s) {
+  return __expf(-hsic_sqdist(X, nrm, i, j, d, xs) * inv_s);
 }
 
 // All threads call.  X, Y: [m][xs] samples; nx, ny, rk, rl: m floats each (filled here); red >= 64 floats.

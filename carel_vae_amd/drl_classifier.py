@@ -453,10 +453,80 @@ def permutation_test_mat(matrix, n_1, n_2, n_permutations, a00=1, a01=0, a11=1, 
     return (pval, stats, c) if return_stats else pval
 
 
-def mmd_two_sample_test(sample_1, sample_2, alphas, n_permutations=1000, eps=1e-5, labels=None, generator=None, return_stats=False):
+MEDIAN = "median"
+
+
+def _is_median(who, name, value):
+    """True for the string "median"; any other string is refused by name (on every machine, before anything else is looked at)"""
+    if not isinstance(value, str):
+        return False
+    if value != MEDIAN:
+        raise L.CarelError('%s: %s = %r is not a width; the only accepted word is "%s" (the median heuristic), otherwise give numbers'
+                           % (who, name, value, MEDIAN))
+    return True
+
+
+def pdist_quantile(x, q=0.5):
+    """The q-quantile of the squared pairwise distances { D_ij : i < j } of the rows of x [m, d] (2 <= m <= 8192, d <= 64) by numpy's
+    default ("linear") rule, a Python float: the two neighbouring order statistics are selected exactly on the device
+    (carel_pdist_select -- the distances `hsic_gram` exponentiates, bit for bit; the matrix is never stored) and interpolated in
+    double on the host.  One read-back.  THE DEFINITION IS THIS PROJECT'S OWN (the reference has no such function)."""
+    if not torch.cuda.is_available():
+        raise L.CarelError("pdist_quantile runs on the GPU (carel_pdist_select); there is no CPU fallback.")
+    q = float(q)
+    if not 0.0 <= q <= 1.0:
+        raise L.CarelError("pdist_quantile: q must lie in [0, 1] (got %r)" % q)
+    xs = torch.as_tensor(x).detach()
+    dev = xs.device if xs.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    xs = xs.to(dev, torch.float32)
+    if xs.dim() != 2 or xs.shape[0] < 2:
+        raise L.CarelError("pdist_quantile: a sample [m, d] of at least 2 rows is required")
+    if xs.stride(1) != 1:
+        xs = xs.contiguous()
+    n_pairs = xs.shape[0] * (xs.shape[0] - 1) // 2
+    pos = (n_pairs - 1) * q
+    lo = min(int(math.floor(pos)), n_pairs - 1)
+    hi = min(lo + 1, n_pairs - 1)
+    with torch.cuda.device(dev):
+        values, _ = ops.pdist_select(xs, [lo, hi])
+        v_lo, v_hi = (float(v) for v in values.double().cpu())
+    return v_lo + (v_hi - v_lo) * (pos - lo)
+
+
+def median_heuristic(x):
+    """The median-heuristic kernel width of a sample (Gretton et al.): the median squared pairwise distance, `pdist_quantile(x, 0.5)`."""
+    return pdist_quantile(x, 0.5)
+
+
+def _median_width(who, name, sample):
+    med = median_heuristic(sample)
+    if not med > 0.0:
+        raise L.CarelError("%s: the median squared distance behind %s is %r, not > 0 (more than half of the pairs of rows coincide): "
+                           "there is no median-heuristic width; give a number" % (who, name, med))
+    return med
+
+
+def median_alphas(sample_1, sample_2, scales=(1.0,)):
+    """[1 / (scale * median)] for every scale: the `alphas` of the median heuristic for `mmd_two_sample_test` and
+    `MMDStatistic.__call__`, median = `median_heuristic` of the pooled sample [sample_1; sample_2] (the squared distances of
+    `hsic_gram`: no eps, no abs -- 1e-5 away from the MMD kernel's own argument, immaterial to a heuristic)."""
+    if not torch.cuda.is_available():
+        raise L.CarelError("median_alphas runs on the GPU (carel_pdist_select); there is no CPU fallback.")
+    s1, s2 = torch.as_tensor(sample_1).detach(), torch.as_tensor(sample_2).detach()
+    dev = s1.device if s1.is_cuda else (s2.device if s2.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    if s1.dim() != 2 or s2.dim() != 2 or s1.shape[1] != s2.shape[1]:
+        raise L.CarelError("median_alphas: two samples [n_1, d], [n_2, d] are required")
+    med = _median_width("median_alphas", "the pooled sample", torch.cat((s1.to(dev, torch.float32), s2.to(dev, torch.float32)), 0))
+    return [1.0 / (float(s) * med) for s in scales]
+
+
+def mmd_two_sample_test(sample_1, sample_2, alphas, n_permutations=1000, eps=1e-5, labels=None, generator=None, return_stats=False,
+                        return_widths=False):
     """The two-sample test from the samples: the tiled Gram matrix (carel_rbf_gram, n_1 + n_2 <= 8192), then `permutation_test_mat`
     with MMDStatistic's coefficients.  Returns (mmd, pval) as Python floats -- mmd is the observed statistic, what
-    MMDStatistic.__call__ computes -- and with return_stats (mmd, pval, stats, count)."""
+    MMDStatistic.__call__ computes -- and with return_stats (mmd, pval, stats, count).  alphas = "median": `median_alphas` of the two
+    samples, [1 / median squared distance of the pooled sample].  return_widths appends {"alphas": the list used}."""
+    median = _is_median("mmd_two_sample_test", "alphas", alphas)
     if not torch.cuda.is_available():
         raise L.CarelError("mmd_two_sample_test runs on the GPU (carel_rbf_gram, carel_mmd_perm_test); there is no CPU fallback.")
     s1, s2 = torch.as_tensor(sample_1).detach(), torch.as_tensor(sample_2).detach()
@@ -468,11 +538,13 @@ def mmd_two_sample_test(sample_1, sample_2, alphas, n_permutations=1000, eps=1e-
     if s1.shape[0] < 2 or s2.shape[0] < 2:
         raise L.CarelError("mmd_two_sample_test: both samples need at least 2 rows")
     stat = MMDStatistic(s1.shape[0], s2.shape[0])
+    alphas = median_alphas(s1, s2) if median else [float(a) for a in alphas]
     with torch.cuda.device(dev):
-        kern = ops.rbf_gram(s1, s2, [float(a) for a in alphas], eps)
+        kern = ops.rbf_gram(s1, s2, alphas, eps)
     pval, stats, count = stat.pval(kern, n_permutations, labels=labels, generator=generator, return_stats=True)
     mmd = float(stats[0])
-    return (mmd, pval, stats, count) if return_stats else (mmd, pval)
+    out = (mmd, pval, stats, count) if return_stats else (mmd, pval)
+    return out + (dict(alphas=alphas),) if return_widths else out
 
 
 def random_permutations(m, n_permutations, device, generator=None):
@@ -533,11 +605,15 @@ def hsic_permutation_test(K, L_, n_permutations=1000, *, permutations=None, gene
     return (pval, stats, c) if return_stats else pval
 
 
-def hsic_independence_test(x, y, s_x=1.0, s_y=1.0, n_permutations=1000, *, permutations=None, generator=None, return_stats=False):
+def hsic_independence_test(x, y, s_x=1.0, s_y=1.0, n_permutations=1000, *, permutations=None, generator=None, return_stats=False,
+                           return_widths=False):
     """The independence test from the paired samples x [m, d_x], y [m, d_y] (the widths may differ): the tiled Gram matrices
     K = exp(-D(x) / s_x), L = exp(-D(y) / s_y) (carel_hsic_gram, 2 <= m <= 8192), then `hsic_permutation_test`.  Returns (hsic, pval)
     as Python floats -- hsic is the observed statistic, what `HSIC(x, y, s_x, s_y)` computes, and above that operator's row limit
-    (757 at d = 24) this is the only way to it -- and with return_stats (hsic, pval, stats, count)."""
+    (757 at d = 24) this is the only way to it -- and with return_stats (hsic, pval, stats, count).  s_x / s_y = "median": the
+    `median_heuristic` of that sample (a median that is not > 0 is refused).  return_widths appends {"s_x": ..., "s_y": ...}, the
+    widths used."""
+    med_x, med_y = _is_median("hsic_independence_test", "s_x", s_x), _is_median("hsic_independence_test", "s_y", s_y)
     if not torch.cuda.is_available():
         raise L.CarelError("hsic_independence_test runs on the GPU (carel_hsic_gram, carel_hsic_perm_test); there is no CPU fallback.")
     xs, ys = torch.as_tensor(x).detach(), torch.as_tensor(y).detach()
@@ -549,11 +625,16 @@ def hsic_independence_test(x, y, s_x=1.0, s_y=1.0, n_permutations=1000, *, permu
     with torch.cuda.device(dev):
         if permutations is not None:         # refused before the Gram launches, not after them
             permutations = _checked_permutations("hsic_independence_test", permutations, int(n_permutations), xs.shape[0], dev)
+        if med_x:
+            s_x = _median_width("hsic_independence_test", "s_x", xs)
+        if med_y:
+            s_y = _median_width("hsic_independence_test", "s_y", ys)
         kx, ky = ops.hsic_gram(xs, s_x), ops.hsic_gram(ys, s_y)
     pval, stats, count = hsic_permutation_test(kx, ky, n_permutations, permutations=permutations, generator=generator, return_stats=True,
                                                _checked=permutations is not None)
     hsic = float(stats[0])
-    return (hsic, pval, stats, count) if return_stats else (hsic, pval)
+    out = (hsic, pval, stats, count) if return_stats else (hsic, pval)
+    return out + (dict(s_x=float(s_x), s_y=float(s_y)),) if return_widths else out
 
 
 class _PdistFn(torch.autograd.Function):
@@ -1553,31 +1634,38 @@ class DrlClassifier(nn.Module):
         prob, _ = ops.pair_probs_draws(lat, eps_e, eps_c, W["pair_classifier.weight"], W["pair_classifier.bias"], self.opt.ec_dim)
         return (prob, (eps_e, eps_c)) if return_noise else prob
 
-    def latent_two_sample_test(self, lat, n_permutations=1000, noise=None, alphas=None, labels=None, generator=None, return_stats=False):
+    def latent_two_sample_test(self, lat, n_permutations=1000, noise=None, alphas=None, labels=None, generator=None, return_stats=False,
+                               return_widths=False):
         """Are the emotion and the cause latents distinguishable (extension)?  The permutation two-sample test of `mmd_two_sample_test`
         on z_e, z_c [N, ec_dim] sampled from the latents of `pair_latents` the way draw 0 of `pair_probabilities_from` samples them
         (noise = (eps_e, eps_c) replays a chosen draw; without it one is drawn like a forward call's).  alphas defaults to the kernel
-        width of the model's own MMD loss term.  2 N <= 8192.  Returns (mmd, pval), with return_stats (mmd, pval, stats, count)."""
+        width of the model's own MMD loss term; "median" takes the median heuristic of the sampled z the test then runs on (same
+        noise, same call).  2 N <= 8192.  Returns (mmd, pval), with return_stats (mmd, pval, stats, count); return_widths appends
+        {"alphas": the list used}."""
+        _is_median("latent_two_sample_test", "alphas", alphas)
         self._require_cuda()
         D = self.opt.ec_dim
         eps_e, eps_c = self._draws_noise(lat.device, 1, noise)
         z = ops.sample_latents(lat, eps_e[0].contiguous(), eps_c[0].contiguous(), D)
         return mmd_two_sample_test(z[:, :D], z[:, D:], ops.MODEL_MMD_ALPHAS if alphas is None else alphas, n_permutations, eps=1e-5,
-                                   labels=labels, generator=generator, return_stats=return_stats)
+                                   labels=labels, generator=generator, return_stats=return_stats, return_widths=return_widths)
 
     def latent_independence_test(self, lat, n_permutations=1000, noise=None, s_e=1.0, s_c=1.0, permutations=None, generator=None,
-                                 return_stats=False):
+                                 return_stats=False, return_widths=False):
         """Are the emotion and the cause latent of the same pair independent (extension)?  The permutation independence test of
         `hsic_independence_test` on z_e, z_c [N, ec_dim] sampled from the latents of `pair_latents` exactly as
         `latent_two_sample_test` samples them (noise = (eps_e, eps_c) replays a chosen draw; without it one is drawn like a forward
-        call's).  s_e, s_c: the kernel widths of the two Gram matrices.  N <= 8192.  Returns (hsic, pval), with return_stats
-        (hsic, pval, stats, count)."""
+        call's).  s_e, s_c: the kernel widths of the two Gram matrices; "median" takes the median heuristic of the sampled z_e / z_c
+        the test then runs on (same noise, same call).  N <= 8192.  Returns (hsic, pval), with return_stats (hsic, pval, stats,
+        count); return_widths appends {"s_e": ..., "s_c": ...}, the widths used."""
+        _is_median("latent_independence_test", "s_e", s_e), _is_median("latent_independence_test", "s_c", s_c)
         self._require_cuda()
         D = self.opt.ec_dim
         eps_e, eps_c = self._draws_noise(lat.device, 1, noise)
         z = ops.sample_latents(lat, eps_e[0].contiguous(), eps_c[0].contiguous(), D)
-        return hsic_independence_test(z[:, :D], z[:, D:], s_e, s_c, n_permutations, permutations=permutations, generator=generator,
-                                      return_stats=return_stats)
+        out = hsic_independence_test(z[:, :D], z[:, D:], s_e, s_c, n_permutations, permutations=permutations, generator=generator,
+                                     return_stats=return_stats, return_widths=return_widths)
+        return out[:-1] + (dict(s_e=out[-1]["s_x"], s_c=out[-1]["s_y"]),) if return_widths else out
 
     def draw_counts(self, lat, labels, n_draws, groups=None, noise=None, return_noise=False, n_groups=None):
         """int64 [K, G, 3]: TP / FP / FN of `prob > 0.5` (numpy's .round() of a probability, ref :282: exactly 0.5 predicts 0) against

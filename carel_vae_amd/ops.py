@@ -562,6 +562,33 @@ def hsic_perm_test(K, Lm, perms):
     return stats, count
 
 
+def pdist_select(x, ranks):
+    """carel_pdist_select: the exact order statistics of { D_ij : i < j }, D the squared distances `hsic_gram` exponentiates (bit for
+    bit), of the rows of x f32 [m, d] (2 <= m <= 8192, d <= 64), without the matrix.  ranks: up to 8 host integers in
+    [0, m (m-1) / 2), 0-based.  Returns (values f32 [n], counts int64 [n, 2] = #{D < v}, #{D == v}) on the device; nothing is read
+    back."""
+    _chk_cuda(x)
+    if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1:
+        raise L.CarelError("pdist_select: a float32 [m, d] sample with contiguous rows is required")
+    ranks = [int(r) for r in ranks]
+    n = len(ranks)
+    if not 1 <= n <= L.PDIST_SELECT_MAX_RANKS:
+        raise L.CarelError("pdist_select: 1 to %d ranks are required (got %d)" % (L.PDIST_SELECT_MAX_RANKS, n))
+    m = x.shape[0]
+    lib = L.load()
+    a = L.PdistSelectArgs()
+    a.x, a.ldx, a.m, a.d, a.n_ranks = x.data_ptr(), x.stride(0), m, x.shape[1], n
+    for q, r in enumerate(ranks):
+        a.ranks[q] = r
+    values = torch.empty(n, device=x.device, dtype=torch.float32)
+    counts = torch.empty((n, 2), device=x.device, dtype=torch.int64)
+    nbytes = int(lib.carel_pdist_select_workspace_bytes(m, n))
+    work = torch.empty(max(nbytes, 8) // 8, device=x.device, dtype=torch.float64)
+    a.values, a.counts, a.workspace, a.workspace_bytes = values.data_ptr(), counts.data_ptr(), work.data_ptr(), nbytes
+    L.check(lib.carel_pdist_select(C.byref(a), L.current_stream()), "carel_pdist_select")
+    return values, counts
+
+
 def hsic_backward(x, y, grad, s_x=1.0, s_y=1.0):
     a = _hsic_args(x, y, s_x, s_y)
     gx, gy = torch.empty(x.shape, device=x.device, dtype=torch.float32), torch.empty(y.shape, device=x.device, dtype=torch.float32)

@@ -881,6 +881,40 @@ int64_t carel_hsic_perm_workspace_bytes(int32_t m, int32_t n_permutations);
 int carel_hsic_perm_test(const carel_hsic_perm_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Exact order statistics of the squared pairwise distances of one sample (the median-heuristic kernel width of the two permutation
+ * tests above).  The reference has no such function, so this DEFINITION IS THE PROJECT'S OWN (parity unpinned).
+ *   x f32 [m, d], row stride ldx >= d;  D_ij = n_i + n_j - 2 dot_ij in float32 with the norms and the dot product by the fmaf chains
+ *   of hsic_kern (csrc/hsic_device.h, hsic_sqdist): the number carel_hsic_gram multiplies by -1/s, bit for bit -- bitwise symmetric,
+ *   D_ii = +0, no abs, so near-duplicate rows far from the origin can give a slightly negative value;
+ *   the population is the multiset { D_ij : i < j } of N = m (m-1) / 2 values (the matrix is never stored);
+ *   for each of the n_ranks ranks r (HOST values, 0-based, in [0, N), repeats allowed):  values[q] = v_r, the r-th smallest element,
+ *   with the bits of one of the D_ij (a -0 is returned as +0);  counts[q] = { #{D < v_r}, #{D == v_r} }, so that
+ *   counts[q][0] <= r < counts[q][0] + counts[q][1].
+ * A three-pass radix select (11 / 11 / 10 bits) on an order-preserving key of the float, the distances recomputed per pass from rows
+ * staged in LDS; all counting is integer (atomicAdd on integers only), so two runs give the same bits.  Precondition: finite inputs
+ * (a NaN distance ranks above +inf and comes back as a NaN; no input can make an index leave a histogram).  csrc/pdist_select.hip;
+ * the bound against float64: tests/pdist_select_restate.py.
+ * workspace: carel_pdist_select_workspace_bytes(m, n_ranks) bytes of device memory, 16-byte aligned, fully rewritten by every call; the
+ * function is pure host code and returns 0 for a shape outside the limits.
+ * Limits: 2 <= m <= 8192, 1 <= d <= 64, 1 <= n_ranks <= 8.  Seven launches on `stream`, no allocation, no host synchronisation.
+ * Errors before the first launch (nothing is written): a NULL struct / x / values / workspace, ldx < d, a rank outside [0, N), a
+ * workspace smaller than stated or not 16-byte aligned -> CAREL_ERR_ARG; m, d or n_ranks outside the limits -> CAREL_ERR_SHAPE.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct carel_pdist_select_args {
+  const void* x;            /* f32 [m, d], row stride ldx */
+  int64_t ldx;
+  int32_t m, d;
+  int32_t n_ranks;
+  int64_t ranks[8];         /* host values */
+  void* values;             /* f32 [n_ranks] */
+  void* counts;             /* i64 [n_ranks][2] = below, equal; may be NULL */
+  void* workspace;
+  int64_t workspace_bytes;
+} carel_pdist_select_args;
+int64_t carel_pdist_select_workspace_bytes(int32_t m, int32_t n_ranks);
+int carel_pdist_select(const carel_pdist_select_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * VI / CLUB head (ablation script drl_classifier_ec_vi.py).  z = [e | c] f32 [B, 2*ec_dim] are the sampled emotion /
  * cause embeddings; net[8] = approximation network p(e|c): ec_mu.0.weight, ec_mu.0.bias, ec_mu.2.weight, ec_mu.2.bias,
  * ec_log_var.0.weight, .0.bias, .2.weight, .2.bias (:156-163).
