@@ -309,6 +309,12 @@ SIGNATURES = {
     "carel_pdist_bwd": (C.c_int, [C.POINTER(PdistArgs), C.c_void_p]),
     "carel_hsic_fwd": (C.c_int, [C.POINTER(HsicArgs), C.c_void_p]),
     "carel_hsic_bwd": (C.c_int, [C.POINTER(HsicArgs), C.c_void_p]),
+    "carel_hsic_tiled_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "carel_hsic_tiled_fwd": (C.c_int, [C.POINTER(HsicArgs), C.c_void_p, C.c_void_p]),
+    "carel_hsic_tiled_bwd": (C.c_int, [C.POINTER(HsicArgs), C.c_void_p, C.c_void_p]),
+    "carel_rbf_mmd_tiled_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "carel_rbf_mmd_tiled_fwd": (C.c_int, [C.POINTER(MmdArgs), C.c_void_p, C.c_void_p]),
+    "carel_rbf_mmd_tiled_bwd": (C.c_int, [C.POINTER(MmdArgs), C.c_void_p, C.c_void_p]),
     "carel_hsic_gram": (C.c_int, [C.POINTER(HsicGramArgs), C.c_void_p]),
     "carel_hsic_perm_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "carel_hsic_perm_test": (C.c_int, [C.POINTER(HsicPermArgs), C.c_void_p]),

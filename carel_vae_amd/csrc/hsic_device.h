@@ -23,6 +23,29 @@ __device__ __forceinline__ float hsic_kern(const float* X, const float* nrm, int
   return __expf(-hsic_sqdist(X, nrm, i, j, d, xs) * inv_s);
 }
 
+// hsic_sqdist / hsic_kern of row i against the NJ rows j0, j0 + 1, ... at once: per pair the same chain (k ascending, the same
+// expression for the distance), with row i read once per k instead of once per pair and the NJ dot products in registers.
+template <int NJ>
+__device__ __forceinline__ void hsic_sqdist_row(const float* X, const float* nrm, int i, int j0, int d, int xs, float (&out)[NJ]) {
+  float dot[NJ];
+#pragma unroll
+  for (int q = 0; q < NJ; ++q) dot[q] = 0.f;
+  for (int k = 0; k < d; ++k) {
+    const float xi = X[i * xs + k];
+#pragma unroll
+    for (int q = 0; q < NJ; ++q) dot[q] = fmaf(xi, X[(j0 + q) * xs + k], dot[q]);
+  }
+#pragma unroll
+  for (int q = 0; q < NJ; ++q) out[q] = nrm[i] + nrm[j0 + q] - 2.0f * dot[q];
+}
+
+template <int NJ>
+__device__ __forceinline__ void hsic_kern_row(const float* X, const float* nrm, int i, int j0, int d, int xs, float inv_s, float (&out)[NJ]) {
+  hsic_sqdist_row<NJ>(X, nrm, i, j0, d, xs, out);
+#pragma unroll
+  for (int q = 0; q < NJ; ++q) out[q] = __expf(-out[q] * inv_s);
+}
+
 // All threads call.  X, Y: [m][xs] samples; nx, ny, rk, rl: m floats each (filled here); red >= 64 floats.
 // Returns HSIC in every thread; tot[0] = TK, tot[1] = TL are left in red[60], red[61].
 __device__ inline float hsic_forward_block(const HsicCfg& c, const float* X, const float* Y, float* nx, float* ny, float* rk,

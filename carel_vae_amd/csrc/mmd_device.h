@@ -36,6 +36,33 @@ __device__ __forceinline__ float mmd_pair_kernel(const MmdCfg& c, const float* Z
   return kv;
 }
 
+// mmd_pair_kernel of row i against the NJ rows j0, j0 + 1, ... at once: per pair the same chains (k ascending, the alphas in turn), with
+// row i read once per k and the NJ dot products in registers.  GRAD false: out = the kernel values; true: out = the signed
+// sum_a alpha * K_a that mmd_pair_kernel returns through dcoef.
+template <int NJ, bool GRAD>
+__device__ __forceinline__ void mmd_pair_row(const MmdCfg& c, const float* Z, const float* nrm, int i, int j0, float (&out)[NJ]) {
+  float dot[NJ];
+#pragma unroll
+  for (int q = 0; q < NJ; ++q) dot[q] = 0.f;
+  for (int k = 0; k < c.d; ++k) {
+    const float zi = Z[i * c.zs + k];
+#pragma unroll
+    for (int q = 0; q < NJ; ++q) dot[q] = fmaf(zi, Z[(j0 + q) * c.zs + k], dot[q]);
+  }
+#pragma unroll
+  for (int q = 0; q < NJ; ++q) {
+    const float d2 = nrm[i] + nrm[j0 + q] - 2.0f * dot[q];
+    const float ad = c.eps + fabsf(d2);
+    float kv = 0.f, dc = 0.f;
+    for (int a = 0; a < c.n_alphas; ++a) {
+      const float e = expf(-c.alphas[a] * ad);
+      kv += e;
+      dc = fmaf(c.alphas[a], e, dc);
+    }
+    out[q] = GRAD ? ((d2 > 0.f) ? dc : ((d2 < 0.f) ? -dc : 0.f)) : kv;
+  }
+}
+
 // All threads of the block call this.  `nrm` (n floats) is filled here.  red: >= 64 floats LDS scratch.
 // Returns mmd (valid in every thread).  If kernels_out != null the full Gram matrix is written (ret_matrix).
 __device__ inline float mmd_forward_block(const MmdCfg& c, const float* Z, float* nrm, float* red,

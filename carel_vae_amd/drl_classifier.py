@@ -609,8 +609,8 @@ def hsic_independence_test(x, y, s_x=1.0, s_y=1.0, n_permutations=1000, *, permu
                            return_widths=False):
     """The independence test from the paired samples x [m, d_x], y [m, d_y] (the widths may differ): the tiled Gram matrices
     K = exp(-D(x) / s_x), L = exp(-D(y) / s_y) (carel_hsic_gram, 2 <= m <= 8192), then `hsic_permutation_test`.  Returns (hsic, pval)
-    as Python floats -- hsic is the observed statistic, what `HSIC(x, y, s_x, s_y)` computes, and above that operator's row limit
-    (757 at d = 24) this is the only way to it -- and with return_stats (hsic, pval, stats, count).  s_x / s_y = "median": the
+    as Python floats -- hsic is the observed statistic, what `HSIC(x, y, s_x, s_y)` computes (differentiably, up to the same 8192
+    rows; here from the stored matrices in double) -- and with return_stats (hsic, pval, stats, count).  s_x / s_y = "median": the
     `median_heuristic` of that sample (a median that is not > 0 is refused).  return_widths appends {"s_x": ..., "s_y": ...}, the
     widths used."""
     med_x, med_y = _is_median("hsic_independence_test", "s_x", s_x), _is_median("hsic_independence_test", "s_y", s_y)

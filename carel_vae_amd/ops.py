@@ -41,10 +41,50 @@ def gemm(A, B, form, epi, M, N, K, *, splits=1, out_bf16=None, out2_bf16=None, o
     L.check(L.load().carel_gemm_bf16(C.byref(a), L.current_stream()), "carel_gemm_bf16")
 
 
+# ---- the single-workgroup statistic operators keep both samples in one workgroup's LDS (160 KB); above that the tiled entries take over
+SINGLE_LDS_FLOATS = 160 * 1024 // 4
+STAT_TILED_MAX_ROWS = 8192
+
+
+def _largest(fits):
+    n = 1
+    while fits(n + 1):
+        n += 1
+    return n
+
+
+def mmd_single_limit(d):
+    """the largest n1 + n2 that carel_rbf_mmd_fwd/bwd accept at feature width d (mmd_prepare of csrc/mmd.hip): 1572 at d = 24"""
+    return _largest(lambda n: 64 + ((n + 3) & ~3) + n * (d | 1) <= SINGLE_LDS_FLOATS)
+
+
+def hsic_single_limit(d):
+    """the largest m that carel_hsic_fwd/bwd accept at feature width d (hsic_launch of csrc/hsic.hip): 757 at d = 24"""
+    return _largest(lambda m: 64 + 4 * ((m + 3) & ~3) + 2 * m * (d | 1) <= SINGLE_LDS_FLOATS)
+
+
+def _mmd_goes_tiled(s1, s2):
+    """above the single-workgroup limit and inside the tiled one; every other shape keeps the single-workgroup entry and its errors"""
+    n, d = s1.shape[0] + s2.shape[0], s1.shape[1]
+    return 1 <= d <= 64 and mmd_single_limit(d) < n <= STAT_TILED_MAX_ROWS and s1.shape[0] >= 2 and s2.shape[0] >= 2
+
+
+def _hsic_goes_tiled(x):
+    m, d = x.shape
+    return 1 <= d <= 64 and hsic_single_limit(d) < m <= STAT_TILED_MAX_ROWS
+
+
+def _work(nbytes, device):
+    return torch.empty(max(int(nbytes), 8) // 8 + 1, device=device, dtype=torch.float64)
+
+
 def rbf_mmd(s1, s2, alphas, eps=1e-5, ret_matrix=False):
-    """MMDStatistic.__call__ forward (ref :547-569).  Returns (mmd[1], kernels or None)."""
+    """MMDStatistic.__call__ forward (ref :547-569).  Returns (mmd[1], kernels or None).  Samples that one workgroup's LDS holds go to
+    carel_rbf_mmd_fwd, larger ones (n1 + n2 <= 8192) to `rbf_mmd_tiled`, the matrix then from `rbf_gram` (the same expression)."""
     _chk_cuda(s1, s2)
     a = _mmd_args(s1, s2, alphas, eps)
+    if _mmd_goes_tiled(s1, s2):
+        return rbf_mmd_tiled(s1, s2, alphas, eps), (rbf_gram(s1, s2, alphas, eps) if ret_matrix else None)
     out = torch.empty(1, device=s1.device, dtype=torch.float32)
     n = s1.shape[0] + s2.shape[0]
     kern = torch.empty((n, n), device=s1.device, dtype=torch.float32) if ret_matrix else None
@@ -55,12 +95,41 @@ def rbf_mmd(s1, s2, alphas, eps=1e-5, ret_matrix=False):
 
 
 def rbf_mmd_backward(s1, s2, alphas, grad, eps=1e-5):
+    if _mmd_goes_tiled(s1, s2):
+        return rbf_mmd_tiled_backward(s1, s2, alphas, grad, eps)
     a = _mmd_args(s1, s2, alphas, eps)
     g1 = torch.empty((s1.shape[0], s1.shape[1]), device=s1.device, dtype=torch.float32)
     g2 = torch.empty((s2.shape[0], s2.shape[1]), device=s1.device, dtype=torch.float32)
     grad = grad.reshape(1).to(torch.float32).contiguous()
     a.grad_mmd, a.g1, a.g2 = grad.data_ptr(), g1.data_ptr(), g2.data_ptr()
     L.check(L.load().carel_rbf_mmd_bwd(C.byref(a), L.current_stream()), "carel_rbf_mmd_bwd")
+    return g1, g2
+
+
+def rbf_mmd_tiled(s1, s2, alphas, eps=1e-5):
+    """carel_rbf_mmd_tiled_fwd: the statistic of `rbf_mmd` summed tile by tile on the whole chip, n1, n2 >= 2, n1 + n2 <= 8192.
+    Returns mmd f32 [1] on the device."""
+    _chk_cuda(s1, s2)
+    a = _mmd_args(s1, s2, alphas, eps)
+    lib = L.load()
+    out = torch.empty(1, device=s1.device, dtype=torch.float32)
+    work = _work(lib.carel_rbf_mmd_tiled_workspace_bytes(a.n1, a.n2, a.d), s1.device)
+    a.mmd_out = out.data_ptr()
+    L.check(lib.carel_rbf_mmd_tiled_fwd(C.byref(a), work.data_ptr(), L.current_stream()), "carel_rbf_mmd_tiled_fwd")
+    return out
+
+
+def rbf_mmd_tiled_backward(s1, s2, alphas, grad, eps=1e-5):
+    """carel_rbf_mmd_tiled_bwd: (g1 [n1, d], g2 [n2, d]) = grad * d mmd / d s; grad None = 1."""
+    _chk_cuda(s1, s2)
+    a = _mmd_args(s1, s2, alphas, eps)
+    lib = L.load()
+    g1 = torch.empty((s1.shape[0], s1.shape[1]), device=s1.device, dtype=torch.float32)
+    g2 = torch.empty((s2.shape[0], s2.shape[1]), device=s1.device, dtype=torch.float32)
+    grad = None if grad is None else grad.reshape(1).to(torch.float32).contiguous()
+    work = _work(lib.carel_rbf_mmd_tiled_workspace_bytes(a.n1, a.n2, a.d), s1.device)
+    a.grad_mmd, a.g1, a.g2 = None if grad is None else grad.data_ptr(), g1.data_ptr(), g2.data_ptr()
+    L.check(lib.carel_rbf_mmd_tiled_bwd(C.byref(a), work.data_ptr(), L.current_stream()), "carel_rbf_mmd_tiled_bwd")
     return g1, g2
 
 
@@ -516,11 +585,37 @@ def _hsic_args(x, y, s_x, s_y):
 
 
 def hsic(x, y, s_x=1.0, s_y=1.0):
+    """carel_hsic_fwd while one workgroup's LDS holds both samples (m <= 757 at d = 24), `hsic_tiled` above (m <= 8192)."""
     a = _hsic_args(x, y, s_x, s_y)
+    if _hsic_goes_tiled(x):
+        return hsic_tiled(x, y, s_x, s_y)
     out = torch.empty(1, device=x.device, dtype=torch.float32)
     a.hsic_out = out.data_ptr()
     L.check(L.load().carel_hsic_fwd(C.byref(a), L.current_stream()), "carel_hsic_fwd")
     return out
+
+
+def hsic_tiled(x, y, s_x=1.0, s_y=1.0):
+    """carel_hsic_tiled_fwd: the statistic of `hsic` summed tile by tile on the whole chip, 2 <= m <= 8192.  Returns f32 [1]."""
+    a = _hsic_args(x, y, s_x, s_y)
+    lib = L.load()
+    out = torch.empty(1, device=x.device, dtype=torch.float32)
+    work = _work(lib.carel_hsic_tiled_workspace_bytes(a.m, a.d), x.device)
+    a.hsic_out = out.data_ptr()
+    L.check(lib.carel_hsic_tiled_fwd(C.byref(a), work.data_ptr(), L.current_stream()), "carel_hsic_tiled_fwd")
+    return out
+
+
+def hsic_tiled_backward(x, y, grad, s_x=1.0, s_y=1.0):
+    """carel_hsic_tiled_bwd: (gx, gy) [m, d] = grad * d hsic / d (x, y); grad None = 1."""
+    a = _hsic_args(x, y, s_x, s_y)
+    lib = L.load()
+    gx, gy = torch.empty(x.shape, device=x.device, dtype=torch.float32), torch.empty(y.shape, device=x.device, dtype=torch.float32)
+    grad = None if grad is None else grad.reshape(1).to(torch.float32).contiguous()
+    work = _work(lib.carel_hsic_tiled_workspace_bytes(a.m, a.d), x.device)
+    a.grad_hsic, a.gx, a.gy = None if grad is None else grad.data_ptr(), gx.data_ptr(), gy.data_ptr()
+    L.check(lib.carel_hsic_tiled_bwd(C.byref(a), work.data_ptr(), L.current_stream()), "carel_hsic_tiled_bwd")
+    return gx, gy
 
 
 def hsic_gram(x, s=1.0):
@@ -590,6 +685,8 @@ def pdist_select(x, ranks):
 
 
 def hsic_backward(x, y, grad, s_x=1.0, s_y=1.0):
+    if x.dim() == 2 and _hsic_goes_tiled(x):
+        return hsic_tiled_backward(x, y, grad, s_x, s_y)
     a = _hsic_args(x, y, s_x, s_y)
     gx, gy = torch.empty(x.shape, device=x.device, dtype=torch.float32), torch.empty(y.shape, device=x.device, dtype=torch.float32)
     grad = grad.reshape(1).to(torch.float32).contiguous()

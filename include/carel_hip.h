@@ -825,6 +825,33 @@ typedef struct carel_hsic_args {
 int carel_hsic_fwd(const carel_hsic_args* args, void* stream);
 int carel_hsic_bwd(const carel_hsic_args* args, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The two differentiable statistics on samples of up to 8192 rows (csrc/stat_tiled.hip, stat_tiled_device.h).  carel_hsic_fwd/bwd and
+ * carel_rbf_mmd_fwd/bwd keep both samples in one workgroup's LDS and stop there (HSIC m = 757 at d = 24, MMD n1 + n2 = 1572); these
+ * take the same structs, evaluate element by element the same expressions (hsic_kern of csrc/hsic_device.h, mmd_pair_kernel of
+ * csrc/mmd_device.h; the centred coefficients of hsic_backward_row, the weights of mmd_backward_row) and differ in the order of the
+ * sums only: workgroups own 64 x 64 tiles of rows x partner rows, neither matrix is stored, LDS per workgroup is below 64 KB whatever
+ * the sample size.  A thread adds 16 kernel values in float; everything across threads and tiles (the three HSIC sums, the row sums RK_i,
+ * RL_i, TK, TL; the three MMD block sums) is added in double in an order fixed by indices and rounded once.  A gradient element is a
+ * float chain over the partners of one run of tiles, then the runs in turn.  No atomics: two calls give the same bits.
+ *   HSIC  2 <= m <= 8192;   MMD  n1, n2 >= 2, n1 + n2 <= 8192;   1 <= d <= 64, row strides >= d, 1..8 alphas, widths > 0.
+ *   grad_hsic / grad_mmd NULL = an upstream gradient of 1.  kernels_out of carel_mmd_args is NOT read by the tiled entries
+ *   (carel_rbf_gram writes the matrix).  The forward entries write hsic_out / mmd_out only, the backward entries gx, gy / g1, g2 only.
+ *   work: carel_hsic_tiled_workspace_bytes(m, d) / carel_rbf_mmd_tiled_workspace_bytes(n1, n2, d) bytes of device memory, 8-byte
+ *   aligned, rewritten by every call; with T = ceil(rows / 64), S = ceil(T / ceil(T / min(T, max(1, 1024 / T)))) (integer division):
+ *     HSIC  8 (T^2 + 3 ceil(m / 256)) + 4 (4 + 2 * 64 T + 2 T * 64 T + 2 S m d)        MMD  8 * 3 T^2 + 4 S (n1 + n2) d
+ *   Both are pure host functions and return 0 for a shape outside the limits.
+ * HSIC: three launches forward, six backward; MMD: two and two.  No allocation, no host synchronisation.  Every check comes before
+ * the first launch: a NULL struct / sample / output / workspace, a misaligned workspace, a row stride below d, a width <= 0,
+ * n_alphas outside 1..8 -> CAREL_ERR_ARG; m, n1, n2 or d outside the limits -> CAREL_ERR_SHAPE; the message names the entry point.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t carel_hsic_tiled_workspace_bytes(int32_t m, int32_t d);
+int carel_hsic_tiled_fwd(const carel_hsic_args* args, void* work, void* stream);
+int carel_hsic_tiled_bwd(const carel_hsic_args* args, void* work, void* stream);
+int64_t carel_rbf_mmd_tiled_workspace_bytes(int32_t n1, int32_t n2, int32_t d);
+int carel_rbf_mmd_tiled_fwd(const carel_mmd_args* args, void* work, void* stream);
+int carel_rbf_mmd_tiled_bwd(const carel_mmd_args* args, void* work, void* stream);
+
 /* The Gram matrix of HSIC alone, tiled: k_out[i][j] = K_ij = exp(-D(x)_ij / s) f32 [m, m] (row stride ldk >= m; the padding is not
  * written), each element by the expression carel_hsic_fwd evaluates (hsic_kern of csrc/hsic_device.h: the norms and the dot product by
  * the same fmaf chains, __expf(-(n_i + n_j - 2 dot) / s)), so the matrix is bitwise symmetric and its diagonal is exactly 1.
