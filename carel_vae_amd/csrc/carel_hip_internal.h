@@ -19,6 +19,15 @@ namespace carel {
 
 int set_error(int code, const char* fmt, ...);
 int check_launch(const char* what);
+// a caller's workspace: not null, `align`-byte aligned and, where the entry takes its size, at least `need` bytes
+inline int check_workspace(const char* who, const void* p, int align, int64_t have = 0, int64_t need = 0) {
+  if (!p) return set_error(CAREL_ERR_ARG, "%s: null workspace", who);
+  if (have < need) return set_error(CAREL_ERR_ARG, "%s: workspace of %lld bytes, %lld needed", who, (long long)have, (long long)need);
+  if ((uintptr_t)p % align) return set_error(CAREL_ERR_ARG, "%s: the workspace must be %d-byte aligned", who, align);
+  return CAREL_OK;
+}
+// mmd_perm.hip: count[0] = #{p >= 1 : stats[p] >= stats[0]} of the np1 doubles of a permutation test, one workgroup (both tests end with it)
+void perm_count(const double* stats, int np1, int* count, hipStream_t stream);
 int slab_reduce_multi(const void* slabs, void* out, int64_t n, const void* slabs2, void* out2, int64_t n2, int splits, const void* partials,
                       int nparts, void* dgamma, void* dbeta, void* dbias, hipStream_t stream);   // gemm.hip: weight slabs + bias partials + LayerNorm partials in one launch
 #ifdef CAREL_EXPERIMENTS

@@ -20,18 +20,22 @@
 //                        loads, lost a wave per SIMD and were slower, 3.87 ms).  A lane's order is (row, column block); lanes by
 //                        butterfly, the four waves in turn -> part[slab][P+1].  G = 4 while four rows of L fit 48 KB (m <= HG_M4 =
 //                        3072: the Kc row and its conversion are shared by four permutations), else 1 (32 KB at 8 192).
-//   hsic_stats_kernel    adds the slabs in turn and divides; hsic_count_kernel compares the doubles and counts (integers).
+//   hsic_stats_kernel    adds the slabs in turn and divides; perm_count (the count kernel of mmd_perm.hip, the same kernel for both
+//                        tests) compares the doubles and counts (integers).
 // No atomics, no host synchronisation; a permutation has the same bits in whatever row of `perms` it stands (every slot of a group
 // runs the same instructions in the same order) and on every run.
 //
-// carel_hsic_gram.  64 x 64 tiles; the 64 + 64 sample rows of a tile and their squared norms sit in LDS (33 KB whatever m is) and every
-// element is hsic_kern of hsic_device.h, symmetric in its two rows; on the diagonal dot is the norm's own chain, so the argument is -0.
+// carel_hsic_gram.  64 x 64 tiles; the 64 + 64 sample rows of a tile and their squared norms are staged by the shared prologue
+// (st_stage_pair of stat_tile_device.h: 33 KB of LDS whatever m is; ps_sweep_kernel makes the same call, so its distances are these by
+// construction) and every element is hsic_kern of hsic_device.h, symmetric in its two rows; on the diagonal dot is the norm's own
+// chain, so the argument is -0.
 #include "carel_hip_internal.h"
 #include "hsic_device.h"
+#include "stat_tile_device.h"
 
 namespace carel {
 
-constexpr int HP_MAX_M = 8192, HP_MAX_P = 65535;
+constexpr int HP_MAX_P = 65535;
 constexpr int HG_SLAB = 64;      // rows i per workgroup of the gather kernel (tests/hsic_perm_restate.py: SLAB)
 constexpr int HG_M4 = 3072;      // four staged rows of L up to here (48 KB), one above (GROUP_M)
 constexpr int HC_ROWS = 64;      // rows per column-sum part
@@ -66,8 +70,7 @@ __global__ __launch_bounds__(256) void hsic_rowsum_kernel(HsicPermArgs a) {
   const float* row = a.K + (long)i * a.ldk;
   double s = 0.0;
   for (int j = lane; j < a.m; j += 64) s += (double)row[j];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  s = wave_sum_double(s);
   if (lane == 0) a.rsum[i] = s;
 }
 
@@ -121,7 +124,7 @@ __global__ __launch_bounds__(256) void hsic_gather_kernel(HsicPermArgs a) {
   const int t = threadIdx.x, m = a.m, m4 = a.m4;
   const int i0 = blockIdx.y * HG_SLAB, i1 = min(i0 + HG_SLAB, m);
   const int p0 = blockIdx.x * G;
-  constexpr int MAXM = G == 4 ? HG_M4 : HP_MAX_M;
+  constexpr int MAXM = G == 4 ? HG_M4 : STAT_MAX_ROWS;
   constexpr int TRIPS = MAXM / 1024;         // column blocks of 1024 a thread visits: 3 / 8
   constexpr int TS = MAXM / 256;             // floats of a staged row a thread carries: 12 / 32
   uint2 w[G][TRIPS];                         // this thread's pi_j, four u16 per column block, loaded ONCE for the slab's rows
@@ -190,9 +193,7 @@ __global__ __launch_bounds__(256) void hsic_gather_kernel(HsicPermArgs a) {
   }
 #pragma unroll
   for (int g = 0; g < G; ++g) {
-    double v = acc[g];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    const double v = wave_sum_double(acc[g]);
     if ((t & 63) == 0) red[(t >> 6) * G + g] = v;
   }
   __syncthreads();
@@ -207,46 +208,19 @@ __global__ __launch_bounds__(256) void hsic_stats_kernel(const double* __restric
   stats[p] = s / den;
 }
 
-__global__ __launch_bounds__(1024) void hsic_count_kernel(const double* __restrict__ stats, int np1, int* __restrict__ count) {
-  __shared__ int red[16];
-  const double s0 = stats[0];
-  int cnt = 0;
-  for (int p = 1 + threadIdx.x; p < np1; p += 1024) cnt += stats[p] >= s0 ? 1 : 0;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int tot = 0;
-    for (int w = 0; w < 16; ++w) tot += red[w];
-    count[0] = tot;
-  }
-}
-
 // ---- the Gram matrix of one sample, tiled
-constexpr int HGR_TILE = 64;
 struct HsicGramArgs { const float* x; long ldx; int m, d, xs; float inv_s; float* out; long ldk; };
 
-__global__ __launch_bounds__(256) void hsic_gram_kernel(HsicGramArgs a) {
-  __shared__ float X[2 * HGR_TILE * 65];     // rows 0..63: the tile's rows i, 64..127: its columns j; row stride xs = d | 1 <= 65
-  __shared__ float nrm[2 * HGR_TILE];
+__global__ __launch_bounds__(ST_THREADS) void hsic_gram_kernel(HsicGramArgs a) {
+  __shared__ float X[2 * ST_TILE * ST_XS];   // rows 0..63: the tile's rows i, 64..127: its columns j; row stride xs = d | 1
+  __shared__ float nrm[2 * ST_TILE];
   const int t = threadIdx.x, m = a.m, d = a.d, xs = a.xs;
-  const int i0 = blockIdx.y * HGR_TILE, j0 = blockIdx.x * HGR_TILE;
-  for (int e = t; e < 2 * HGR_TILE * d; e += 256) {
-    const int r = e / d, k = e - r * d;
-    const int g = r < HGR_TILE ? i0 + r : j0 + (r - HGR_TILE);
-    X[r * xs + k] = g < m ? a.x[(long)g * a.ldx + k] : 0.f;
-  }
-  __syncthreads();
-  if (t < 2 * HGR_TILE) {
-    float s = 0.f;
-    for (int k = 0; k < d; ++k) s = fmaf(X[t * xs + k], X[t * xs + k], s);      // the chain of hsic_forward_block
-    nrm[t] = s;
-  }
-  __syncthreads();
-  for (int e = t; e < HGR_TILE * HGR_TILE; e += 256) {
-    const int ii = e / HGR_TILE, jj = e - ii * HGR_TILE;
-    if (i0 + ii < m && j0 + jj < m) a.out[(long)(i0 + ii) * a.ldk + (j0 + jj)] = hsic_kern(X, nrm, ii, HGR_TILE + jj, d, xs, a.inv_s);
+  const int i0 = blockIdx.y * ST_TILE, j0 = blockIdx.x * ST_TILE;
+  const float* x = a.x; const long ldx = a.ldx;
+  st_stage_pair(X, nrm, [=](int g) { return x + (long)g * ldx; }, i0, j0, m, d, xs);
+  for (int e = t; e < ST_TILE * ST_TILE; e += ST_THREADS) {
+    const int ii = e / ST_TILE, jj = e - ii * ST_TILE;
+    if (i0 + ii < m && j0 + jj < m) a.out[(long)(i0 + ii) * a.ldk + (j0 + jj)] = hsic_kern(X, nrm, ii, ST_TILE + jj, d, xs, a.inv_s);
   }
 }
 
@@ -259,7 +233,7 @@ static int64_t hp_colparts(int64_t m) { return (m + HC_ROWS - 1) / HC_ROWS; }
 static int64_t hp_m4(int64_t m) { return (m + 3) & ~(int64_t)3; }
 
 extern "C" int64_t carel_hsic_perm_workspace_bytes(int32_t m, int32_t n_permutations) {
-  if (m < 2 || m > HP_MAX_M || n_permutations < 1 || n_permutations > HP_MAX_P) return 0;
+  if (m < 2 || m > STAT_MAX_ROWS || n_permutations < 1 || n_permutations > HP_MAX_P) return 0;
   const int64_t np1 = (int64_t)n_permutations + 1, m4 = hp_m4(m);
   // Kc f32 [m][m4], idx u16 [P+1][m4], then the doubles: part [slabs][P+1], R [m], C [m], T [1], the column-sum parts [parts][m]
   return 4 * (int64_t)m * m4 + 2 * np1 * m4 + 8 * (hp_slabs(m) * np1 + 2 * (int64_t)m + 1 + hp_colparts(m) * m);
@@ -269,15 +243,12 @@ extern "C" int carel_hsic_perm_test(const carel_hsic_perm_args* a, void* stream_
   hipStream_t stream = (hipStream_t)stream_;
   const char* who = "carel_hsic_perm_test";
   if (!a || !a->k || !a->l || !a->perms || !a->stats || !a->count || !a->workspace) return set_error(CAREL_ERR_ARG, "%s: null pointer", who);
-  if (a->m < 2 || a->m > HP_MAX_M) return set_error(CAREL_ERR_SHAPE, "%s: m must be in 2..%d (got %d)", who, HP_MAX_M, a->m);
+  if (a->m < 2 || a->m > STAT_MAX_ROWS) return set_error(CAREL_ERR_SHAPE, "%s: m must be in 2..%d (got %d)", who, STAT_MAX_ROWS, a->m);
   if (a->n_permutations < 1 || a->n_permutations > HP_MAX_P)
     return set_error(CAREL_ERR_SHAPE, "%s: n_permutations must be in 1..%d (got %d)", who, HP_MAX_P, a->n_permutations);
   if (a->ldk < a->m || a->ldl < a->m)
     return set_error(CAREL_ERR_ARG, "%s: row strides %lld, %lld below m = %d", who, (long long)a->ldk, (long long)a->ldl, a->m);
-  const int64_t need = carel_hsic_perm_workspace_bytes(a->m, a->n_permutations);
-  if (a->workspace_bytes < need)
-    return set_error(CAREL_ERR_ARG, "%s: workspace of %lld bytes, %lld needed", who, (long long)a->workspace_bytes, (long long)need);
-  if ((uintptr_t)a->workspace % 16) return set_error(CAREL_ERR_ARG, "%s: the workspace must be 16-byte aligned", who);
+  if (int rc = check_workspace(who, a->workspace, 16, a->workspace_bytes, carel_hsic_perm_workspace_bytes(a->m, a->n_permutations))) return rc;
   HsicPermArgs k;
   k.K = (const float*)a->k; k.ldk = a->ldk; k.L = (const float*)a->l; k.ldl = a->ldl; k.perms = (const int*)a->perms;
   k.m = a->m; k.m4 = (int)hp_m4(a->m); k.np1 = a->n_permutations + 1;
@@ -302,7 +273,7 @@ extern "C" int carel_hsic_perm_test(const carel_hsic_perm_args* a, void* stream_
   const double m1 = (double)(k.m - 1);
   hipLaunchKernelGGL(hsic_stats_kernel, dim3((unsigned)((k.np1 + 255) / 256)), dim3(256), 0, stream, (const double*)k.part, slabs, k.np1, m1 * m1,
                      (double*)a->stats);
-  hipLaunchKernelGGL(hsic_count_kernel, dim3(1), dim3(1024), 0, stream, (const double*)a->stats, k.np1, (int*)a->count);
+  perm_count((const double*)a->stats, k.np1, (int*)a->count, stream);
   return check_launch("carel_hsic_perm_test");
 }
 
@@ -310,14 +281,14 @@ extern "C" int carel_hsic_gram(const carel_hsic_gram_args* a, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   const char* who = "carel_hsic_gram";
   if (!a || !a->x || !a->k_out) return set_error(CAREL_ERR_ARG, "%s: null pointer", who);
-  if (a->m < 2 || a->m > HP_MAX_M) return set_error(CAREL_ERR_SHAPE, "%s: m must be in 2..%d (got %d)", who, HP_MAX_M, a->m);
-  if (a->d < 1 || a->d > 64) return set_error(CAREL_ERR_SHAPE, "%s: d must be in 1..64 (got %d)", who, a->d);
+  if (a->m < 2 || a->m > STAT_MAX_ROWS) return set_error(CAREL_ERR_SHAPE, "%s: m must be in 2..%d (got %d)", who, STAT_MAX_ROWS, a->m);
+  if (a->d < 1 || a->d > STAT_MAX_D) return set_error(CAREL_ERR_SHAPE, "%s: d must be in 1..%d (got %d)", who, STAT_MAX_D, a->d);
   if (!(a->s > 0.f)) return set_error(CAREL_ERR_ARG, "%s: the kernel width must be positive", who);
   if (a->ldx < a->d) return set_error(CAREL_ERR_ARG, "%s: row stride of x below d", who);
   if (a->ldk < a->m) return set_error(CAREL_ERR_ARG, "%s: row stride of k_out below m", who);
   HsicGramArgs k;
   k.x = (const float*)a->x; k.ldx = a->ldx; k.m = a->m; k.d = a->d; k.xs = a->d | 1; k.inv_s = 1.0f / a->s; k.out = (float*)a->k_out; k.ldk = a->ldk;
-  const int tiles = (k.m + HGR_TILE - 1) / HGR_TILE;
-  hipLaunchKernelGGL(hsic_gram_kernel, dim3(tiles, tiles), dim3(256), 0, stream, k);
+  const int tiles = (k.m + ST_TILE - 1) / ST_TILE;
+  hipLaunchKernelGGL(hsic_gram_kernel, dim3(tiles, tiles), dim3(ST_THREADS), 0, stream, k);
   return check_launch("carel_hsic_gram");
 }

@@ -2,8 +2,7 @@
 // (drl_classifier_ec_mmd_final_mul.py:547-569, :580-589) and of its autograd backward.
 // One workgroup of 1024 threads; both samples live in LDS (padded odd row stride), the Gram matrix is
 // never written unless ret_matrix asks for it; block sums use wave shuffles + an LDS stage.
-#include "carel_hip_internal.h"
-#include "mmd_device.h"
+#include "stat_host.h"
 
 namespace carel {
 
@@ -148,9 +147,7 @@ static int mmd_prepare(const carel_mmd_args* a, MmdKernelArgs* k, size_t* lds, c
   *lds = (size_t)(64 + ((n + 3) & ~3) + (size_t)n * zs) * sizeof(float);
   if (*lds > 160 * 1024) return set_error(CAREL_ERR_SHAPE, "%s: (n1+n2)*d too large for one LDS (%zu bytes)", who, *lds);
   k->s1 = (const float*)a->s1; k->s2 = (const float*)a->s2; k->ld1 = a->ld1; k->ld2 = a->ld2;
-  k->cfg.n1 = a->n1; k->cfg.n2 = a->n2; k->cfg.d = a->d; k->cfg.zs = zs; k->cfg.n_alphas = a->n_alphas;
-  for (int i = 0; i < 8; ++i) k->cfg.alphas[i] = i < a->n_alphas ? a->alphas[i] : 0.f;
-  k->cfg.eps = a->eps;
+  fill_mmd_cfg(&k->cfg, a, zs);
   k->mmd_out = (float*)a->mmd_out; k->kernels_out = (float*)a->kernels_out;
   k->grad_mmd = (const float*)a->grad_mmd; k->g1 = (float*)a->g1; k->g2 = (float*)a->g2;
   return CAREL_OK;

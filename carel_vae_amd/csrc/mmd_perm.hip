@@ -13,13 +13,18 @@
 // f32 chain is never longer than PT_CHUNK, everything after it is double, and every order is fixed by indices: a labelling gets the
 // same bits wherever it stands in `labels` and on every run.  The two lane halves (rows 4h + ...) are added once at the end; the
 // workgroup's sums go to part[row tile][3][P+1], perm_stats_kernel adds the row tiles in turn and forms stats, perm_count_kernel
-// compares the doubles and counts (integers).  perm_pack_kernel first turns the label bytes into one 32-bit word per labelling and
-// chunk, so a lane of the tile kernel loads its labelling's 32 partners as one word.  No atomics, no host synchronisation.
+// compares the doubles and counts (integers; perm_count: the HSIC test of hsic_perm.hip ends with the same kernel).  perm_pack_kernel
+// first turns the label bytes into one 32-bit word per labelling and chunk, so a lane of the tile kernel loads its labelling's 32
+// partners as one word.  No atomics, no host synchronisation.
 //
 // carel_rbf_gram.  64 x 64 tiles; the 64 + 64 sample rows of a tile and their squared norms sit in LDS (33 KB whatever n is) and every
 // element is mmd_pair_kernel of mmd_device.h, whose arithmetic is symmetric in its two rows: out[i][j] and out[j][i] have the same bits.
-#include "carel_hip_internal.h"
-#include "mmd_device.h"
+// The tile, the thread count and the limits are those of stat_tile_device.h; the staging loop and the norm chain are this kernel's
+// own, NOT st_stage_pair: with the two-sample row lambda the shared loop selects base pointer and stride per element and measured
+// 1 % slower (0.0627 -> 0.0634 ms at n = 3 876, d = 24), while this loop branches per sample with scalar strides.  Same values, same
+// places, the same k-ascending fmaf chain as st_norms.
+#include "stat_host.h"
+#include "stat_tile_device.h"
 #include "tail_device.h"
 
 namespace carel {
@@ -28,7 +33,7 @@ constexpr int PT_ROWS = 32;      // matrix rows per workgroup: one MFMA tile
 constexpr int PT_LABS = 128;     // labellings per workgroup: 32 per wave
 constexpr int PT_CHUNK = 32;     // partners j per f32 chain (tests/perm_restate.py: CHUNK)
 constexpr int PT_LD = 33;        // LDS row stride in floats: rows 33 apart and the two k of a step 1 apart fall into different banks
-constexpr int PERM_MAX_N = 8192, PERM_MAX_P = 65535;
+constexpr int PERM_MAX_P = 65535;
 static_assert(PT_ROWS == 32 && PT_CHUNK == PT_ROWS && PT_CHUNK % 2 == 0, "one staging loop fills both matrix tiles");
 
 struct PermArgs {
@@ -162,34 +167,32 @@ __global__ __launch_bounds__(1024) void perm_count_kernel(const double* __restri
 }
 
 // ---- the Gram matrix of two samples, tiled
-constexpr int GR_TILE = 64;
-constexpr int GRAM_MAX_N = 8192;
 struct GramArgs { const float* s1; const float* s2; long ld1, ld2; MmdCfg cfg; float* out; };
 
-__global__ __launch_bounds__(256) void rbf_gram_kernel(GramArgs a) {
-  __shared__ float Z[2 * GR_TILE * 65];      // rows 0..63: the tile's rows i, 64..127: its columns j; row stride cfg.zs = d | 1 <= 65
-  __shared__ float nrm[2 * GR_TILE];
+__global__ __launch_bounds__(ST_THREADS) void rbf_gram_kernel(GramArgs a) {
+  __shared__ float Z[2 * ST_TILE * ST_XS];   // rows 0..63: the tile's rows i, 64..127: its columns j; row stride cfg.zs = d | 1
+  __shared__ float nrm[2 * ST_TILE];
   const MmdCfg& c = a.cfg;
   const int n = c.n1 + c.n2, t = threadIdx.x;
-  const int i0 = blockIdx.y * GR_TILE, j0 = blockIdx.x * GR_TILE;
-  for (int e = t; e < 2 * GR_TILE * c.d; e += 256) {
+  const int i0 = blockIdx.y * ST_TILE, j0 = blockIdx.x * ST_TILE;
+  for (int e = t; e < 2 * ST_TILE * c.d; e += ST_THREADS) {
     const int r = e / c.d, k = e - r * c.d;
-    const int g = (r < GR_TILE ? i0 + r : j0 + (r - GR_TILE));
+    const int g = (r < ST_TILE ? i0 + r : j0 + (r - ST_TILE));
     float v = 0.f;
     if (g < n) v = g < c.n1 ? a.s1[(long)g * a.ld1 + k] : a.s2[(long)(g - c.n1) * a.ld2 + k];
     Z[r * c.zs + k] = v;
   }
   __syncthreads();
-  if (t < 2 * GR_TILE) {
+  if (t < 2 * ST_TILE) {
     float s = 0.f;
     for (int k = 0; k < c.d; ++k) s = fmaf(Z[t * c.zs + k], Z[t * c.zs + k], s);
     nrm[t] = s;
   }
   __syncthreads();
-  for (int e = t; e < GR_TILE * GR_TILE; e += 256) {
-    const int ii = e / GR_TILE, jj = e - ii * GR_TILE;
+  for (int e = t; e < ST_TILE * ST_TILE; e += ST_THREADS) {
+    const int ii = e / ST_TILE, jj = e - ii * ST_TILE;
     if (i0 + ii < n && j0 + jj < n)
-      a.out[(size_t)(i0 + ii) * n + (j0 + jj)] = mmd_pair_kernel(c, Z, nrm, ii, GR_TILE + jj, nullptr);
+      a.out[(size_t)(i0 + ii) * n + (j0 + jj)] = mmd_pair_kernel(c, Z, nrm, ii, ST_TILE + jj, nullptr);
   }
 }
 
@@ -206,10 +209,14 @@ __global__ __launch_bounds__(256) void latent_sample_kernel(const float* __restr
 
 using namespace carel;
 
+void carel::perm_count(const double* stats, int np1, int* count, hipStream_t stream) {
+  hipLaunchKernelGGL(perm_count_kernel, dim3(1), dim3(1024), 0, stream, stats, np1, count);
+}
+
 static int perm_tiles(int n) { return (n + PT_ROWS - 1) / PT_ROWS; }
 
 extern "C" int64_t carel_mmd_perm_workspace_bytes(int32_t n, int32_t n_permutations) {
-  if (n < 4 || n > PERM_MAX_N || n_permutations < 1 || n_permutations > PERM_MAX_P) return 0;
+  if (n < 4 || n > STAT_MAX_ROWS || n_permutations < 1 || n_permutations > PERM_MAX_P) return 0;
   const int64_t cells = (int64_t)perm_tiles(n) * ((int64_t)n_permutations + 1);      // (row tile, labelling): three doubles and one label word
   return 8 * (3 * cells + (cells + 1) / 2);
 }
@@ -220,13 +227,12 @@ extern "C" int carel_mmd_perm_test(const carel_mmd_perm_args* a, void* stream_) 
   if (!a || !a->matrix || !a->labels || !a->stats || !a->count || !a->workspace) return set_error(CAREL_ERR_ARG, "%s: null pointer", who);
   if (a->n1 < 2 || a->n2 < 2) return set_error(CAREL_ERR_SHAPE, "%s: n1,n2 must be >= 2", who);
   const long n = (long)a->n1 + a->n2;
-  if (n > PERM_MAX_N) return set_error(CAREL_ERR_SHAPE, "%s: n1 + n2 must be <= %d (got %ld)", who, PERM_MAX_N, n);
+  if (n > STAT_MAX_ROWS) return set_error(CAREL_ERR_SHAPE, "%s: n1 + n2 must be <= %d (got %ld)", who, STAT_MAX_ROWS, n);
   if (a->n_permutations < 1 || a->n_permutations > PERM_MAX_P)
     return set_error(CAREL_ERR_SHAPE, "%s: n_permutations must be in 1..%d (got %d)", who, PERM_MAX_P, a->n_permutations);
   if (a->ldm < n) return set_error(CAREL_ERR_ARG, "%s: row stride %lld below n = %ld", who, (long long)a->ldm, n);
   const int64_t need = carel_mmd_perm_workspace_bytes((int32_t)n, a->n_permutations);
-  if (a->workspace_bytes < need)
-    return set_error(CAREL_ERR_ARG, "%s: workspace of %lld bytes, %lld needed", who, (long long)a->workspace_bytes, (long long)need);
+  if (int rc = check_workspace(who, a->workspace, 1, a->workspace_bytes, need)) return rc;      // (1: this entry demands no alignment)
   PermArgs k;
   k.M = (const float*)a->matrix; k.ldm = a->ldm; k.labels = (const unsigned char*)a->labels;
   k.n = (int)n; k.np1 = a->n_permutations + 1; k.part = (double*)a->workspace;
@@ -236,7 +242,7 @@ extern "C" int carel_mmd_perm_test(const carel_mmd_perm_args* a, void* stream_) 
   hipLaunchKernelGGL(perm_tile_kernel, dim3(tiles, (k.np1 + PT_LABS - 1) / PT_LABS), dim3(256), 0, stream, k);
   hipLaunchKernelGGL(perm_stats_kernel, dim3((k.np1 + 255) / 256), dim3(256), 0, stream, (const double*)k.part, tiles, k.np1, a->a00, a->a01,
                      a->a11, (double*)a->stats);
-  hipLaunchKernelGGL(perm_count_kernel, dim3(1), dim3(1024), 0, stream, (const double*)a->stats, k.np1, (int*)a->count);
+  perm_count((const double*)a->stats, k.np1, (int*)a->count, stream);
   return check_launch("carel_mmd_perm_test");
 }
 
@@ -246,18 +252,16 @@ extern "C" int carel_rbf_gram(const carel_mmd_args* a, void* stream_) {
   if (!a || !a->s1 || !a->s2 || !a->kernels_out) return set_error(CAREL_ERR_ARG, "%s: null pointer", who);
   if (a->n1 < 1 || a->n2 < 1) return set_error(CAREL_ERR_SHAPE, "%s: empty sample", who);
   const long n = (long)a->n1 + a->n2;
-  if (n > GRAM_MAX_N) return set_error(CAREL_ERR_SHAPE, "%s: n1 + n2 must be <= %d (got %ld)", who, GRAM_MAX_N, n);
-  if (a->d < 1 || a->d > 64) return set_error(CAREL_ERR_SHAPE, "%s: d must be in 1..64 (got %d)", who, a->d);
+  if (n > STAT_MAX_ROWS) return set_error(CAREL_ERR_SHAPE, "%s: n1 + n2 must be <= %d (got %ld)", who, STAT_MAX_ROWS, n);
+  if (a->d < 1 || a->d > STAT_MAX_D) return set_error(CAREL_ERR_SHAPE, "%s: d must be in 1..%d (got %d)", who, STAT_MAX_D, a->d);
   if (a->n_alphas < 1 || a->n_alphas > 8) return set_error(CAREL_ERR_ARG, "%s: n_alphas must be in 1..8", who);
   if (a->ld1 < a->d || a->ld2 < a->d) return set_error(CAREL_ERR_ARG, "%s: row stride below d", who);
   GramArgs k;
   k.s1 = (const float*)a->s1; k.s2 = (const float*)a->s2; k.ld1 = a->ld1; k.ld2 = a->ld2;
-  k.cfg.n1 = a->n1; k.cfg.n2 = a->n2; k.cfg.d = a->d; k.cfg.zs = a->d | 1; k.cfg.n_alphas = a->n_alphas;
-  for (int i = 0; i < 8; ++i) k.cfg.alphas[i] = i < a->n_alphas ? a->alphas[i] : 0.f;
-  k.cfg.eps = a->eps;
+  fill_mmd_cfg(&k.cfg, a, a->d | 1);
   k.out = (float*)a->kernels_out;
-  const int tiles = (int)((n + GR_TILE - 1) / GR_TILE);
-  hipLaunchKernelGGL(rbf_gram_kernel, dim3(tiles, tiles), dim3(256), 0, stream, k);
+  const int tiles = (int)((n + ST_TILE - 1) / ST_TILE);
+  hipLaunchKernelGGL(rbf_gram_kernel, dim3(tiles, tiles), dim3(ST_THREADS), 0, stream, k);
   return check_launch("rbf_gram_kernel");
 }
 

@@ -5,7 +5,8 @@
 //   ps_zero_kernel       the whole workspace (state and histograms) to 0: every call rewrites all of it.
 //   ps_sweep_kernel<P>   a workgroup owns one 64 x 64 tile of the upper triangle (tile row <= tile column) and, in passes 1 and 2, one
 //                        SLOT (blockIdx.y): a key prefix that at least one rank is still following.  It stages the tile's 64 + 64 rows
-//                        and their norms in LDS as hsic_gram_kernel does, recomputes the 4096 distances (in the diagonal tile only
+//                        and their norms in LDS as hsic_gram_kernel does -- by construction: both call st_stage_pair of
+//                        stat_tile_device.h -- recomputes the 4096 distances (in the diagonal tile only
 //                        i < j counts), and adds 1 to an LDS histogram of the next 11 / 11 / 10 key bits for every element whose
 //                        higher bits equal the slot's prefix; the non-empty bins then go to the slot's global histogram.  Integer
 //                        atomicAdd only: the sums do not depend on the order, two runs give the same bits.
@@ -21,6 +22,7 @@
 // PS_WAVE_AGGREGATE (a one-off build's flag): lanes of a wave with equal bins add once.  Off: it measured slower.
 #include "carel_hip_internal.h"
 #include "hsic_device.h"
+#include "stat_tile_device.h"
 
 #ifndef PS_WAVE_AGGREGATE
 #define PS_WAVE_AGGREGATE 0
@@ -28,8 +30,7 @@
 
 namespace carel {
 
-constexpr int PS_MAX_M = 8192, PS_MAX_D = 64, PS_MAX_RANKS = 8;
-constexpr int PS_TILE = 64;
+constexpr int PS_MAX_RANKS = 8;
 constexpr int PS_BINS = 2048;                // bins of passes 0 and 1 (11 bits); pass 2 uses 1024 (10 bits)
 constexpr int PS_STATE_BYTES = 256;
 
@@ -82,10 +83,10 @@ __global__ __launch_bounds__(256) void ps_zero_kernel(unsigned* w, long words) {
 }
 
 template <int PASS>
-__global__ __launch_bounds__(256) void ps_sweep_kernel(PsArgs a) {
+__global__ __launch_bounds__(ST_THREADS) void ps_sweep_kernel(PsArgs a) {
   constexpr int BINS = PASS == 2 ? 1024 : PS_BINS;
-  __shared__ float X[2 * PS_TILE * 65];      // rows 0..63: the tile's rows i, 64..127: its columns j; row stride xs = d | 1 <= 65
-  __shared__ float nrm[2 * PS_TILE];
+  __shared__ float X[2 * ST_TILE * ST_XS];   // rows 0..63: the tile's rows i, 64..127: its columns j; row stride xs = d | 1
+  __shared__ float nrm[2 * ST_TILE];
   __shared__ unsigned hist[BINS];
   const int t = threadIdx.x, m = a.m, d = a.d, xs = a.xs;
   const int slot = PASS == 0 ? 0 : (int)blockIdx.y;
@@ -93,23 +94,13 @@ __global__ __launch_bounds__(256) void ps_sweep_kernel(PsArgs a) {
   const unsigned want = PASS == 0 ? 0u : a.state->slot_prefix[slot];
   int ti = 0, rem = (int)blockIdx.x;         // the blockIdx.x-th tile of the upper triangle, row by row
   while (rem >= a.tiles - ti) { rem -= a.tiles - ti; ++ti; }
-  const int i0 = ti * PS_TILE, j0 = (ti + rem) * PS_TILE;
-  for (int b = t; b < BINS; b += 256) hist[b] = 0u;
-  for (int e = t; e < 2 * PS_TILE * d; e += 256) {
-    const int r = e / d, k = e - r * d;
-    const int g = r < PS_TILE ? i0 + r : j0 + (r - PS_TILE);
-    X[r * xs + k] = g < m ? a.x[(long)g * a.ldx + k] : 0.f;
-  }
-  __syncthreads();
-  if (t < 2 * PS_TILE) {
-    float s = 0.f;
-    for (int k = 0; k < d; ++k) s = fmaf(X[t * xs + k], X[t * xs + k], s);      // the chain of hsic_forward_block
-    nrm[t] = s;
-  }
-  __syncthreads();
-  for (int e = t; e < PS_TILE * PS_TILE; e += 256) {       // a wave: one row ii, 64 columns jj
-    const int ii = e / PS_TILE, jj = e - ii * PS_TILE;
-    const unsigned key = ps_key(hsic_sqdist(X, nrm, ii, PS_TILE + jj, d, xs));
+  const int i0 = ti * ST_TILE, j0 = (ti + rem) * ST_TILE;
+  for (int b = t; b < BINS; b += ST_THREADS) hist[b] = 0u;
+  const float* x = a.x; const long ldx = a.ldx;
+  st_stage_pair(X, nrm, [=](int g) { return x + (long)g * ldx; }, i0, j0, m, d, xs);
+  for (int e = t; e < ST_TILE * ST_TILE; e += ST_THREADS) {       // a wave: one row ii, 64 columns jj
+    const int ii = e / ST_TILE, jj = e - ii * ST_TILE;
+    const unsigned key = ps_key(hsic_sqdist(X, nrm, ii, ST_TILE + jj, d, xs));
     bool on = i0 + ii < j0 + jj && j0 + jj < m;
     unsigned bin;
     if (PASS == 0) bin = key >> 21;
@@ -119,7 +110,7 @@ __global__ __launch_bounds__(256) void ps_sweep_kernel(PsArgs a) {
   }
   __syncthreads();
   unsigned* out = a.hist[PASS] + (size_t)slot * BINS;
-  for (int b = t; b < BINS; b += 256) {
+  for (int b = t; b < BINS; b += ST_THREADS) {
     const unsigned h = hist[b];
     if (h) atomicAdd(&out[b], h);
   }
@@ -181,7 +172,7 @@ __global__ __launch_bounds__(256) void ps_scan_kernel(PsArgs a) {
 using namespace carel;
 
 extern "C" int64_t carel_pdist_select_workspace_bytes(int32_t m, int32_t n_ranks) {
-  if (m < 2 || m > PS_MAX_M || n_ranks < 1 || n_ranks > PS_MAX_RANKS) return 0;
+  if (m < 2 || m > STAT_MAX_ROWS || n_ranks < 1 || n_ranks > PS_MAX_RANKS) return 0;
   // the state, then u32 histograms: pass 0 [2048], pass 1 [n_ranks][2048], pass 2 [n_ranks][1024]
   return PS_STATE_BYTES + 4 * ((int64_t)PS_BINS + (int64_t)n_ranks * (PS_BINS + 1024));
 }
@@ -190,8 +181,8 @@ extern "C" int carel_pdist_select(const carel_pdist_select_args* a, void* stream
   hipStream_t stream = (hipStream_t)stream_;
   const char* who = "carel_pdist_select";
   if (!a || !a->x || !a->values || !a->workspace) return set_error(CAREL_ERR_ARG, "%s: null pointer", who);
-  if (a->m < 2 || a->m > PS_MAX_M) return set_error(CAREL_ERR_SHAPE, "%s: m must be in 2..%d (got %d)", who, PS_MAX_M, a->m);
-  if (a->d < 1 || a->d > PS_MAX_D) return set_error(CAREL_ERR_SHAPE, "%s: d must be in 1..%d (got %d)", who, PS_MAX_D, a->d);
+  if (a->m < 2 || a->m > STAT_MAX_ROWS) return set_error(CAREL_ERR_SHAPE, "%s: m must be in 2..%d (got %d)", who, STAT_MAX_ROWS, a->m);
+  if (a->d < 1 || a->d > STAT_MAX_D) return set_error(CAREL_ERR_SHAPE, "%s: d must be in 1..%d (got %d)", who, STAT_MAX_D, a->d);
   if (a->ldx < a->d) return set_error(CAREL_ERR_ARG, "%s: row stride of x below d", who);
   if (a->n_ranks < 1 || a->n_ranks > PS_MAX_RANKS)
     return set_error(CAREL_ERR_SHAPE, "%s: n_ranks must be in 1..%d (got %d)", who, PS_MAX_RANKS, a->n_ranks);
@@ -200,12 +191,10 @@ extern "C" int carel_pdist_select(const carel_pdist_select_args* a, void* stream
     if (a->ranks[q] < 0 || a->ranks[q] >= N)
       return set_error(CAREL_ERR_ARG, "%s: rank %lld outside [0, %lld) (m = %d)", who, (long long)a->ranks[q], (long long)N, a->m);
   const int64_t need = carel_pdist_select_workspace_bytes(a->m, a->n_ranks);
-  if (a->workspace_bytes < need)
-    return set_error(CAREL_ERR_ARG, "%s: workspace of %lld bytes, %lld needed", who, (long long)a->workspace_bytes, (long long)need);
-  if ((uintptr_t)a->workspace % 16) return set_error(CAREL_ERR_ARG, "%s: the workspace must be 16-byte aligned", who);
+  if (int rc = check_workspace(who, a->workspace, 16, a->workspace_bytes, need)) return rc;
   PsArgs k;
   k.x = (const float*)a->x; k.ldx = a->ldx; k.m = a->m; k.d = a->d; k.xs = a->d | 1; k.n_ranks = a->n_ranks;
-  k.tiles = (k.m + PS_TILE - 1) / PS_TILE;
+  k.tiles = (k.m + ST_TILE - 1) / ST_TILE;
   for (int q = 0; q < PS_MAX_RANKS; ++q) k.ranks[q] = q < k.n_ranks ? (unsigned)a->ranks[q] : 0u;      // N < 2^25
   k.state = (PsState*)a->workspace;
   k.hist[0] = (unsigned*)((char*)a->workspace + PS_STATE_BYTES);
@@ -215,11 +204,11 @@ extern "C" int carel_pdist_select(const carel_pdist_select_args* a, void* stream
   const long words = (long)(need / 4);
   const unsigned tri = (unsigned)(k.tiles * (k.tiles + 1) / 2);
   hipLaunchKernelGGL(ps_zero_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, (unsigned*)a->workspace, words);
-  hipLaunchKernelGGL(ps_sweep_kernel<0>, dim3(tri), dim3(256), 0, stream, k);
+  hipLaunchKernelGGL(ps_sweep_kernel<0>, dim3(tri), dim3(ST_THREADS), 0, stream, k);
   hipLaunchKernelGGL(ps_scan_kernel<0>, dim3(1), dim3(256), 0, stream, k);
-  hipLaunchKernelGGL(ps_sweep_kernel<1>, dim3(tri, (unsigned)k.n_ranks), dim3(256), 0, stream, k);
+  hipLaunchKernelGGL(ps_sweep_kernel<1>, dim3(tri, (unsigned)k.n_ranks), dim3(ST_THREADS), 0, stream, k);
   hipLaunchKernelGGL(ps_scan_kernel<1>, dim3(1), dim3(256), 0, stream, k);
-  hipLaunchKernelGGL(ps_sweep_kernel<2>, dim3(tri, (unsigned)k.n_ranks), dim3(256), 0, stream, k);
+  hipLaunchKernelGGL(ps_sweep_kernel<2>, dim3(tri, (unsigned)k.n_ranks), dim3(ST_THREADS), 0, stream, k);
   hipLaunchKernelGGL(ps_scan_kernel<2>, dim3(1), dim3(256), 0, stream, k);
   return check_launch("carel_pdist_select");
 }

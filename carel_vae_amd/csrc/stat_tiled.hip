@@ -1,7 +1,9 @@
 // The differentiable statistics on samples of up to 8192 rows: carel_hsic_tiled_fwd/bwd and carel_rbf_mmd_tiled_fwd/bwd.  The same
 // numbers as carel_hsic_fwd/bwd (hsic.hip) and carel_rbf_mmd_fwd/bwd (mmd.hip), element by element the same expressions (the device
 // functions of hsic_device.h / mmd_device.h are called on staged rows, stat_tiled_device.h), summed tile by tile on the whole chip
-// instead of by one workgroup that holds both samples in its LDS.  Neither m x m matrix is stored.
+// instead of by one workgroup that holds both samples in its LDS.  Neither m x m matrix is stored.  The rows are staged and their norms
+// taken by the shared tile prologue of stat_tile_device.h -- the sums kernels by st_stage_pair, the call hsic_gram_kernel and
+// ps_sweep_kernel make, so a tile's K and L elements are that matrix's by construction (rbf_gram_kernel stages with a loop of its own).
 //
 // T = ceil(rows / 64) tiles a side.  The gradient sweeps split the T partner tiles of a row tile into S contiguous runs of `per` tiles
 // (st_split: about 1024 workgroups, at most one run per tile), each run a workgroup that keeps its rows' gradient in registers.
@@ -20,13 +22,11 @@
 //                                  double -> part [T][T][3].   mmd_tiled_total_kernel: one workgroup adds them in index order.
 //        mmd_tiled_grad_kernel     grid (S, T), as for HSIC with the coefficient of mmd_backward_row -> gp [S][n][d]; st_grad_final_kernel.
 // No atomics; every sum has an order fixed by indices, so two runs give the same bits.
-#include "carel_hip_internal.h"
+#include <type_traits>
+#include "stat_host.h"
 #include "stat_tiled_device.h"
 
 namespace carel {
-
-constexpr int ST_MAX_ROWS = 8192;
-constexpr int ST_XS = 65;                  // the widest staged row (d = 64)
 
 struct StHsicArgs {
   const float* x; const float* y; long ldx, ldy;
@@ -57,18 +57,10 @@ __global__ __launch_bounds__(ST_THREADS) void hsic_tiled_sums_kernel(StHsicArgs 
   const int i0 = blockIdx.y * ST_TILE, j0 = blockIdx.x * ST_TILE;
   const float* x = a.x; const float* y = a.y; const long ldx = a.ldx, ldy = a.ldy;
   float kv[ST_CHUNK];
-  st_stage(buf, [=](int g) { return x + (long)g * ldx; }, i0, m, d, xs);
-  st_stage(buf + ST_TILE * xs, [=](int g) { return x + (long)g * ldx; }, j0, m, d, xs);
-  __syncthreads();
-  st_norms(buf, nrm, 2 * ST_TILE, d, xs);
-  __syncthreads();
+  st_stage_pair(buf, nrm, [=](int g) { return x + (long)g * ldx; }, i0, j0, m, d, xs);
   hsic_kern_row<ST_CHUNK>(buf, nrm, ii, ST_TILE + cg * ST_CHUNK, d, xs, a.inv_sx, kv);
   __syncthreads();
-  st_stage(buf, [=](int g) { return y + (long)g * ldy; }, i0, m, d, xs);
-  st_stage(buf + ST_TILE * xs, [=](int g) { return y + (long)g * ldy; }, j0, m, d, xs);
-  __syncthreads();
-  st_norms(buf, nrm, 2 * ST_TILE, d, xs);
-  __syncthreads();
+  st_stage_pair(buf, nrm, [=](int g) { return y + (long)g * ldy; }, i0, j0, m, d, xs);
   const bool iv = i0 + ii < m;
   float sk = 0.f, sl = 0.f, s2 = 0.f, lv[ST_CHUNK];
   hsic_kern_row<ST_CHUNK>(buf, nrm, ii, ST_TILE + cg * ST_CHUNK, d, xs, a.inv_sy, lv);
@@ -125,7 +117,7 @@ __global__ __launch_bounds__(256) void hsic_tiled_total_kernel(StHsicArgs a, int
 
 template <int DQ>
 __global__ __launch_bounds__(ST_THREADS) void hsic_tiled_grad_kernel(StHsicArgs a) {
-  constexpr int XS = 4 * DQ + 1;
+  constexpr int XS = st_grad_xs(DQ);
   __shared__ float lds[3 * ST_TILE * XS];        // the tile's X rows | the partners' rows (X, then Y, then X again) | the tile's Y rows
   __shared__ float nrm[3 * ST_TILE];             // in the same order
   __shared__ float rkc[ST_TILE], rlc[ST_TILE];   // RK, RL of the partners
@@ -214,11 +206,7 @@ __global__ __launch_bounds__(ST_THREADS) void mmd_tiled_sums_kernel(StMmdArgs a)
   const int i0 = blockIdx.y * ST_TILE, j0 = blockIdx.x * ST_TILE, i = i0 + ii;
   const float* s1 = a.s1; const float* s2 = a.s2; const long ld1 = a.ld1, ld2 = a.ld2;
   auto row = [=](int g) { return g < n1 ? s1 + (long)g * ld1 : s2 + (long)(g - n1) * ld2; };
-  st_stage(buf, row, i0, n, d, c.zs);
-  st_stage(buf + ST_TILE * c.zs, row, j0, n, d, c.zs);
-  __syncthreads();
-  st_norms(buf, nrm, 2 * ST_TILE, d, c.zs);
-  __syncthreads();
+  st_stage_pair(buf, nrm, row, i0, j0, n, d, c.zs);
   const bool i1 = i < n1;
   float s11 = 0.f, s22 = 0.f, s12 = 0.f;
   float kv[ST_CHUNK];
@@ -260,7 +248,7 @@ __global__ __launch_bounds__(256) void mmd_tiled_total_kernel(StMmdArgs a) {
 
 template <int DQ>
 __global__ __launch_bounds__(ST_THREADS) void mmd_tiled_grad_kernel(StMmdArgs a) {
-  constexpr int XS = 4 * DQ + 1;
+  constexpr int XS = st_grad_xs(DQ);
   __shared__ float lds[2 * ST_TILE * XS];        // the tile's rows | the partners' rows
   __shared__ float nrm[2 * ST_TILE];
   __shared__ float C[ST_TILE * ST_CS];
@@ -312,6 +300,14 @@ __global__ __launch_bounds__(ST_THREADS) void mmd_tiled_grad_kernel(StMmdArgs a)
 
 using namespace carel;
 
+// f(DQ as a compile-time constant) for the DQ = 4 / 8 / 16 accumulators per thread that hold a row's d features (k = kg + 4 u < 4 DQ)
+template <class F>
+static void st_with_dq(int d, F f) {
+  if (d <= 16) f(std::integral_constant<int, 4>());
+  else if (d <= 32) f(std::integral_constant<int, 8>());
+  else f(std::integral_constant<int, 16>());
+}
+
 static int64_t st_tiles(int64_t rows) { return (rows + ST_TILE - 1) / ST_TILE; }
 
 // partner tiles per gradient workgroup and the number of such runs: about 1024 workgroups, at most one run per tile
@@ -324,7 +320,7 @@ static void st_split(int T, int* per, int* S) {
 }
 
 extern "C" int64_t carel_hsic_tiled_workspace_bytes(int32_t m, int32_t d) {
-  if (m < 2 || m > ST_MAX_ROWS || d < 1 || d > 64) return 0;
+  if (m < 2 || m > STAT_MAX_ROWS || d < 1 || d > STAT_MAX_D) return 0;
   const int64_t T = st_tiles(m), mp = T * ST_TILE, rb = (m + 255) / 256;
   int per, S;
   st_split((int)T, &per, &S);
@@ -333,7 +329,7 @@ extern "C" int64_t carel_hsic_tiled_workspace_bytes(int32_t m, int32_t d) {
 }
 
 extern "C" int64_t carel_rbf_mmd_tiled_workspace_bytes(int32_t n1, int32_t n2, int32_t d) {
-  if (n1 < 2 || n2 < 2 || (int64_t)n1 + n2 > ST_MAX_ROWS || d < 1 || d > 64) return 0;
+  if (n1 < 2 || n2 < 2 || (int64_t)n1 + n2 > STAT_MAX_ROWS || d < 1 || d > STAT_MAX_D) return 0;
   const int64_t n = (int64_t)n1 + n2, T = st_tiles(n);
   int per, S;
   st_split((int)T, &per, &S);
@@ -342,14 +338,13 @@ extern "C" int64_t carel_rbf_mmd_tiled_workspace_bytes(int32_t n1, int32_t n2, i
 
 static int hsic_tiled_launch(const carel_hsic_args* a, void* work, int backward, hipStream_t stream, const char* who) {
   if (!a || !a->x || !a->y) return set_error(CAREL_ERR_ARG, "%s: null sample pointer", who);
-  if (a->m < 2 || a->m > ST_MAX_ROWS) return set_error(CAREL_ERR_SHAPE, "%s: m must be in 2..%d (got %d)", who, ST_MAX_ROWS, a->m);
-  if (a->d < 1 || a->d > 64) return set_error(CAREL_ERR_SHAPE, "%s: d must be in 1..64 (got %d)", who, a->d);
+  if (a->m < 2 || a->m > STAT_MAX_ROWS) return set_error(CAREL_ERR_SHAPE, "%s: m must be in 2..%d (got %d)", who, STAT_MAX_ROWS, a->m);
+  if (a->d < 1 || a->d > STAT_MAX_D) return set_error(CAREL_ERR_SHAPE, "%s: d must be in 1..%d (got %d)", who, STAT_MAX_D, a->d);
   if (!(a->s_x > 0.f) || !(a->s_y > 0.f)) return set_error(CAREL_ERR_ARG, "%s: kernel widths must be positive", who);
   if (a->ldx < a->d || a->ldy < a->d) return set_error(CAREL_ERR_ARG, "%s: row stride below d", who);
   if (!backward && !a->hsic_out) return set_error(CAREL_ERR_ARG, "%s: null output", who);
   if (backward && (!a->gx || !a->gy)) return set_error(CAREL_ERR_ARG, "%s: null gradient output", who);
-  if (!work) return set_error(CAREL_ERR_ARG, "%s: null workspace", who);
-  if ((uintptr_t)work % 8) return set_error(CAREL_ERR_ARG, "%s: the workspace must be 8-byte aligned", who);
+  if (int rc = check_workspace(who, work, 8)) return rc;
   StHsicArgs k;
   k.x = (const float*)a->x; k.y = (const float*)a->y; k.ldx = a->ldx; k.ldy = a->ldy;
   k.m = a->m; k.d = a->d; k.T = (int)st_tiles(a->m); k.mp = k.T * ST_TILE;
@@ -368,9 +363,7 @@ static int hsic_tiled_launch(const carel_hsic_args* a, void* work, int backward,
   hipLaunchKernelGGL(hsic_tiled_total_kernel, dim3(1), dim3(256), 0, stream, k, backward ? 0 : 1);
   if (backward) {
     const dim3 grid(k.S, k.T);
-    if (k.d <= 16) hipLaunchKernelGGL(hsic_tiled_grad_kernel<4>, grid, dim3(ST_THREADS), 0, stream, k);
-    else if (k.d <= 32) hipLaunchKernelGGL(hsic_tiled_grad_kernel<8>, grid, dim3(ST_THREADS), 0, stream, k);
-    else hipLaunchKernelGGL(hsic_tiled_grad_kernel<16>, grid, dim3(ST_THREADS), 0, stream, k);
+    st_with_dq(k.d, [&](auto dq) { hipLaunchKernelGGL(hsic_tiled_grad_kernel<dq()>, grid, dim3(ST_THREADS), 0, stream, k); });
     const long total = (long)k.m * k.d;
     const unsigned blocks = (unsigned)((total + 255) / 256);
     hipLaunchKernelGGL(st_grad_final_kernel, dim3(blocks), dim3(256), 0, stream, (const float*)k.gxp, k.S, (long)k.m, k.d, (long)k.m, k.gx, k.gx);
@@ -389,19 +382,16 @@ extern "C" int carel_hsic_tiled_bwd(const carel_hsic_args* a, void* work, void* 
 static int mmd_tiled_launch(const carel_mmd_args* a, void* work, int backward, hipStream_t stream, const char* who) {
   if (!a || !a->s1 || !a->s2) return set_error(CAREL_ERR_ARG, "%s: null sample pointer", who);
   if (a->n1 < 2 || a->n2 < 2) return set_error(CAREL_ERR_SHAPE, "%s: n1,n2 must be >= 2 (the reference divides by n(n-1))", who);
-  if ((int64_t)a->n1 + a->n2 > ST_MAX_ROWS) return set_error(CAREL_ERR_SHAPE, "%s: n1 + n2 must be <= %d (got %lld)", who, ST_MAX_ROWS, (long long)a->n1 + a->n2);
-  if (a->d < 1 || a->d > 64) return set_error(CAREL_ERR_SHAPE, "%s: d must be in 1..64 (got %d)", who, a->d);
+  if ((int64_t)a->n1 + a->n2 > STAT_MAX_ROWS) return set_error(CAREL_ERR_SHAPE, "%s: n1 + n2 must be <= %d (got %lld)", who, STAT_MAX_ROWS, (long long)a->n1 + a->n2);
+  if (a->d < 1 || a->d > STAT_MAX_D) return set_error(CAREL_ERR_SHAPE, "%s: d must be in 1..%d (got %d)", who, STAT_MAX_D, a->d);
   if (a->n_alphas < 1 || a->n_alphas > 8) return set_error(CAREL_ERR_ARG, "%s: n_alphas must be in 1..8", who);
   if (a->ld1 < a->d || a->ld2 < a->d) return set_error(CAREL_ERR_ARG, "%s: row stride below d", who);
   if (!backward && !a->mmd_out) return set_error(CAREL_ERR_ARG, "%s: null mmd_out", who);
   if (backward && (!a->g1 || !a->g2)) return set_error(CAREL_ERR_ARG, "%s: null gradient output", who);
-  if (!work) return set_error(CAREL_ERR_ARG, "%s: null workspace", who);
-  if ((uintptr_t)work % 8) return set_error(CAREL_ERR_ARG, "%s: the workspace must be 8-byte aligned", who);
+  if (int rc = check_workspace(who, work, 8)) return rc;
   StMmdArgs k;
   k.s1 = (const float*)a->s1; k.s2 = (const float*)a->s2; k.ld1 = a->ld1; k.ld2 = a->ld2;
-  k.cfg.n1 = a->n1; k.cfg.n2 = a->n2; k.cfg.d = a->d; k.cfg.zs = a->d | 1; k.cfg.n_alphas = a->n_alphas;
-  for (int i = 0; i < 8; ++i) k.cfg.alphas[i] = i < a->n_alphas ? a->alphas[i] : 0.f;
-  k.cfg.eps = a->eps;
+  fill_mmd_cfg(&k.cfg, a, a->d | 1);
   const int n = a->n1 + a->n2;
   k.T = (int)st_tiles(n);
   st_split(k.T, &k.per, &k.S);
@@ -413,10 +403,10 @@ static int mmd_tiled_launch(const carel_mmd_args* a, void* work, int backward, h
     hipLaunchKernelGGL(mmd_tiled_total_kernel, dim3(1), dim3(256), 0, stream, k);
   } else {
     const dim3 grid(k.S, k.T);
-    k.cfg.zs = k.cfg.d <= 16 ? 17 : (k.cfg.d <= 32 ? 33 : 65);      // the staged row stride of mmd_tiled_grad_kernel<DQ>: 4 DQ + 1
-    if (k.cfg.d <= 16) hipLaunchKernelGGL(mmd_tiled_grad_kernel<4>, grid, dim3(ST_THREADS), 0, stream, k);
-    else if (k.cfg.d <= 32) hipLaunchKernelGGL(mmd_tiled_grad_kernel<8>, grid, dim3(ST_THREADS), 0, stream, k);
-    else hipLaunchKernelGGL(mmd_tiled_grad_kernel<16>, grid, dim3(ST_THREADS), 0, stream, k);
+    st_with_dq(k.cfg.d, [&](auto dq) {
+      k.cfg.zs = st_grad_xs(dq());               // the staged row stride of the kernel launched: its own XS
+      hipLaunchKernelGGL(mmd_tiled_grad_kernel<dq()>, grid, dim3(ST_THREADS), 0, stream, k);
+    });
     const long total = (long)n * k.cfg.d;
     hipLaunchKernelGGL(st_grad_final_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (const float*)k.gp, k.S, (long)n, k.cfg.d,
                        (long)k.cfg.n1, k.g1, k.g2);

@@ -78,6 +78,19 @@ def _work(nbytes, device):
     return torch.empty(max(int(nbytes), 8) // 8 + 1, device=device, dtype=torch.float64)
 
 
+def _perm_outputs(P, nbytes, device):
+    """the outputs and the workspace of a permutation test: (stats f64 [P+1], count i32 [1], workspace, its size in bytes)"""
+    stats = torch.empty(P + 1, device=device, dtype=torch.float64)
+    count = torch.empty(1, device=device, dtype=torch.int32)
+    return stats, count, _work(nbytes, device), int(nbytes)
+
+
+def _chk_sample(x, who):
+    _chk_cuda(x)
+    if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1:
+        raise L.CarelError("%s: a float32 [m, d] sample with contiguous rows is required" % who)
+
+
 def rbf_mmd(s1, s2, alphas, eps=1e-5, ret_matrix=False):
     """MMDStatistic.__call__ forward (ref :547-569).  Returns (mmd[1], kernels or None).  Samples that one workgroup's LDS holds go to
     carel_rbf_mmd_fwd, larger ones (n1 + n2 <= 8192) to `rbf_mmd_tiled`, the matrix then from `rbf_gram` (the same expression)."""
@@ -210,10 +223,7 @@ def mmd_perm_test(matrix, labels, n1, n2, a00, a01, a11):
     a.matrix, a.ldm, a.labels = matrix.data_ptr(), matrix.stride(0), labels.data_ptr()
     a.n1, a.n2, a.n_permutations = int(n1), int(n2), P
     a.a00, a.a01, a.a11 = float(a00), float(a01), float(a11)
-    stats = torch.empty(P + 1, device=matrix.device, dtype=torch.float64)
-    count = torch.empty(1, device=matrix.device, dtype=torch.int32)
-    nbytes = int(lib.carel_mmd_perm_workspace_bytes(n, P))
-    work = torch.empty(max(nbytes, 8) // 8, device=matrix.device, dtype=torch.float64)
+    stats, count, work, nbytes = _perm_outputs(P, lib.carel_mmd_perm_workspace_bytes(n, P), matrix.device)
     a.stats, a.count, a.workspace, a.workspace_bytes = stats.data_ptr(), count.data_ptr(), work.data_ptr(), nbytes
     L.check(lib.carel_mmd_perm_test(C.byref(a), L.current_stream()), "carel_mmd_perm_test")
     return stats, count
@@ -621,9 +631,7 @@ def hsic_tiled_backward(x, y, grad, s_x=1.0, s_y=1.0):
 def hsic_gram(x, s=1.0):
     """carel_hsic_gram: K = exp(-D(x) / s) f32 [m, m] of the rows of x f32 [m, d], tiled (2 <= m <= 8192, d <= 64): the kernel matrix
     of `hsic`, element by element the same expression, bitwise symmetric, diagonal exactly 1."""
-    _chk_cuda(x)
-    if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1:
-        raise L.CarelError("hsic_gram: a float32 [m, d] sample with contiguous rows is required")
+    _chk_sample(x, "hsic_gram")
     m = x.shape[0]
     out = torch.empty((m, m), device=x.device, dtype=torch.float32)
     a = L.HsicGramArgs()
@@ -648,10 +656,7 @@ def hsic_perm_test(K, Lm, perms):
     a = L.HsicPermArgs()
     a.k, a.ldk, a.l, a.ldl, a.perms = K.data_ptr(), K.stride(0), Lm.data_ptr(), Lm.stride(0), perms.data_ptr()
     a.m, a.n_permutations = m, P
-    stats = torch.empty(P + 1, device=K.device, dtype=torch.float64)
-    count = torch.empty(1, device=K.device, dtype=torch.int32)
-    nbytes = int(lib.carel_hsic_perm_workspace_bytes(m, P))
-    work = torch.empty(max(nbytes, 8) // 8, device=K.device, dtype=torch.float64)
+    stats, count, work, nbytes = _perm_outputs(P, lib.carel_hsic_perm_workspace_bytes(m, P), K.device)
     a.stats, a.count, a.workspace, a.workspace_bytes = stats.data_ptr(), count.data_ptr(), work.data_ptr(), nbytes
     L.check(lib.carel_hsic_perm_test(C.byref(a), L.current_stream()), "carel_hsic_perm_test")
     return stats, count
@@ -662,9 +667,7 @@ def pdist_select(x, ranks):
     bit), of the rows of x f32 [m, d] (2 <= m <= 8192, d <= 64), without the matrix.  ranks: up to 8 host integers in
     [0, m (m-1) / 2), 0-based.  Returns (values f32 [n], counts int64 [n, 2] = #{D < v}, #{D == v}) on the device; nothing is read
     back."""
-    _chk_cuda(x)
-    if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1:
-        raise L.CarelError("pdist_select: a float32 [m, d] sample with contiguous rows is required")
+    _chk_sample(x, "pdist_select")
     ranks = [int(r) for r in ranks]
     n = len(ranks)
     if not 1 <= n <= L.PDIST_SELECT_MAX_RANKS:
@@ -678,7 +681,7 @@ def pdist_select(x, ranks):
     values = torch.empty(n, device=x.device, dtype=torch.float32)
     counts = torch.empty((n, 2), device=x.device, dtype=torch.int64)
     nbytes = int(lib.carel_pdist_select_workspace_bytes(m, n))
-    work = torch.empty(max(nbytes, 8) // 8, device=x.device, dtype=torch.float64)
+    work = _work(nbytes, x.device)
     a.values, a.counts, a.workspace, a.workspace_bytes = values.data_ptr(), counts.data_ptr(), work.data_ptr(), nbytes
     L.check(lib.carel_pdist_select(C.byref(a), L.current_stream()), "carel_pdist_select")
     return values, counts

@@ -23,7 +23,7 @@ import numpy as np
 from tests import stats_restate as R
 
 U = 2.0 ** -24
-TILE = 64               # ps_sweep_kernel: rows and columns of a tile (PS_TILE)
+TILE = 64               # ps_sweep_kernel: rows and columns of a tile (ST_TILE of stat_tile_device.h)
 MAX_M, MAX_D, MAX_RANKS = 8192, 64, 8
 STATE_BYTES, BINS = 256, (2048, 2048, 1024)
 ERR_ARG, ERR_SHAPE = -1, -2
